@@ -9,12 +9,27 @@ i.e. 4 x P*A*d = 1.75 GiB of segments delivered.  Inputs (the fingerprinted
 send buffers) are resident in HBM before the timed region, as in the
 reference (prepare_*_data is untimed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and no more: it sets up (regions,
+fingerprint fill, plans; one verified run per method; at N > 1 the plan-form choice the
+timed steps run with), warms up W steps, times K steps, writes its outputs when
+--dump-outputs is given, and prints the line.  --full adds everything measured beside the
+figure: the reference's CPU baselines (configs[1], and the 8-GPU configurations on an
+8-GPU job), the warm max-total-time report (median of 3 more runs per method), and at
+N > 1 the per-launch roofline pass, the xGMI ceiling / sweeps and BASELINE.json's 8-GPU
+configurations on the job.  The N = 1 roofline comes from one event pair around the timed
+region itself and is in every line.
+
+--dump-outputs DIR: after the timed steps, what the last step delivered -- a fixed, seeded
+sample of every method's receive slots (dump_sample) -- as DIR/method<m>_recv.npy, float32.
+The inputs are the fingerprint, the same for the same arguments, so two builds can be
+compared file by file.
 
 One process per GPU.  N > 1 either under a launcher that sets RANK /
 WORLD_SIZE / LOCAL_RANK (torch.distributed.run, mpiexec) or on its own: with
 no WORLD_SIZE in the environment `--gpus N` makes this process a parent that
-never touches the GPU -- it runs the host-MPI baseline, starts N child
+never touches the GPU -- it runs the host-MPI baseline (--full), starts N child
 processes of itself (one per GPU, RANK / LOCAL_RANK / WORLD_SIZE and one
 rendezvous key set), waits for all of them, fails with the highest child exit
 code if any fails, and prints rank 0's JSON line with the baseline attached.
@@ -52,6 +67,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: the reference's CPU baselines, the warm max-total-time "
+                         "report, and at N > 1 the per-launch roofline pass, the xGMI phase and BASELINE.json's "
+                         "8-GPU configurations (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step delivered (a fixed sample of every "
+                         "method's receive slots) as DIR/<name>.npy, float32")
     ap.add_argument("--procs", type=int, default=32)
     ap.add_argument("--aggs", type=int, default=14)
     ap.add_argument("--size", type=int, default=1 << 20)
@@ -91,7 +113,19 @@ def parse():
                          "has 8 GPUs)")
     ap.add_argument("--cpu-configs-budget", type=float, default=240.0,
                     help="seconds those reference cells may take in all; a cell past it is recorded as skipped")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+def cpu_on(a):
+    """the reference's CPU baselines run: --full, unless --no-cpu-baseline"""
+    return a.full and not a.no_cpu_baseline
+
+
+def baseline_configs_on(a, world):
+    return a.full and (a.baseline_configs == "on" or (a.baseline_configs == "auto" and world == 8))
 
 
 # ---------------------------------------------------------------- watchdog (rank processes)
@@ -191,7 +225,7 @@ def pre_value_allowance(a, rank, world, parent):
     """seconds a rank may legitimately wait before its communicator exists: under a launcher (no
     parent process) rank 0 runs the reference's CPU phases first and writes the RCCL id only after
     them, so every rank allows their budgets"""
-    if parent or a.no_cpu_baseline or world == 1:
+    if parent or not cpu_on(a) or world == 1:
         return 0.0
     return a.cpu_budget + (a.cpu_configs_budget + CPU_GRACE if cpu_configs_on(a, world) else 0.0)
 
@@ -202,9 +236,9 @@ def wall_bound(a, world, parent=False):
     BASELINE-configs phases -- INTEGRATION.md states this bound for the driver's 8-GPU run"""
     pre = pre_value_allowance(a, 0, world, parent) if not parent else 0.0
     post = 0.0
-    if world > 1:
+    if world > 1 and a.full:
         post += a.xgmi_budget
-    if a.baseline_configs == "on" or (a.baseline_configs == "auto" and world == 8):
+    if baseline_configs_on(a, world):
         post += a.baseline_budget + GUARD_GRACE
     return pre + a.watchdog + post
 
@@ -975,7 +1009,7 @@ def spawn_ranks(a):
     stub = os.environ.get("XG_BENCH_CHILD_STUB") == "1"
     methods = [int(x) for x in a.methods.split(",")]
     cpu = cpu_cfg = None
-    if not a.no_cpu_baseline and not stub:
+    if cpu_on(a) and not stub:
         start_heartbeat()             # the children's rank 0 has its own once they start
         phase("cpu baseline")
         cpu = cpu_baseline(a, methods)
@@ -1150,6 +1184,41 @@ def xgmi_phase(xg, ctx, runs, world, nmethods, steps, elapsed, out):
                               "frac": round(bound_ms / (elapsed / steps * 1e3), 4)}
 
 
+# ---------------------------------------------------------------- --dump-outputs
+DUMP_SEED = 20240229
+DUMP_ELEMS = 12 << 20           # float32 elements over all methods: 48 MiB of the 64 MB a dump may take
+DUMP_CHUNK = 4096               # bytes read from each sampled receive slot
+
+
+def dump_sample(method, nslots, d, per_method):
+    """the fixed sample of one method's receive slots: [(slot index, offset in the slot, bytes)], the
+    same for the same arguments (seeded by the method alone) -- every slot when they fit in
+    `per_method` elements, else a sorted random subset; one chunk at a random offset of each"""
+    import numpy as np
+    rng = np.random.RandomState(DUMP_SEED + method)
+    chunk = max(1, min(d, DUMP_CHUNK))
+    n = min(nslots, max(1, per_method // chunk))
+    idx = np.arange(nslots) if n == nslots else np.sort(rng.choice(nslots, n, replace=False))
+    offs = rng.randint(0, d - chunk + 1, size=n)
+    return [(int(i), int(o), chunk) for i, o in zip(idx, offs)]
+
+
+def dump_outputs(dirname, runs, xg, rank, world):
+    """what the timed path's last step left in the receive region of each method (the bytes an
+    aggregator or a receiving rank reads after the exchange), sampled by dump_sample, as
+    DIR/method<m>_recv.npy (N > 1: ..._gpu<g>.npy, this GPU's slots), float32, one row per slot"""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    per_method = DUMP_ELEMS // max(1, len(runs))
+    for r in runs:
+        s = r.sched
+        rows = [np.frombuffer(r.read(xg.BUF_RECV, r.slots[i][3] + o, n), dtype=np.uint8)
+                for i, o, n in dump_sample(s.method, r.nslots, s.d, per_method)]
+        arr = np.stack(rows).astype(np.float32) if rows else np.zeros((0, 0), np.float32)
+        name = "method%d_recv%s.npy" % (s.method, "_gpu%d" % rank if world > 1 else "")
+        np.save(os.path.join(dirname, name), arr)
+
+
 def main():
     a = parse()
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
@@ -1172,7 +1241,7 @@ def main():
     # host-MPI baselines first, before this process touches the GPU (rank 0; a parent
     # process of an N-GPU job runs them itself and passes --no-cpu-baseline)
     cpu = cpu_cfg = None
-    if rank == 0 and not a.no_cpu_baseline:
+    if rank == 0 and cpu_on(a):
         phase("cpu baseline")
         cpu = cpu_baseline(a, methods)
         if cpu_configs_on(a, world):
@@ -1287,13 +1356,14 @@ def main():
                 why[fname] = "verify failed: %d slots (most on one GPU)" % nbad
                 r.close()
                 continue
-            # the reference's report for a warm method: median of 3 more timed runs
-            tw = []
-            for _ in range(3):
-                ctx.barrier()
-                done, post, _wall = r.run_timed()
-                tw.append(max(s.rank_timer(q, done, post, world).total_time for q in range(lo, hi)) if hi > lo else 0.0)
-            tmax = ctx.allreduce_max([sorted(tw)[1]])[0]
+            if a.full:
+                # the reference's report for a warm method: median of 3 more timed runs
+                tw = []
+                for _ in range(3):
+                    ctx.barrier()
+                    done, post, _wall = r.run_timed()
+                    tw.append(max(s.rank_timer(q, done, post, world).total_time for q in range(lo, hi)) if hi > lo else 0.0)
+                tmax = ctx.allreduce_max([sorted(tw)[1]])[0]
             if len(cands) > 1:
                 samples[fname] = [timed_reps(r, 2) for _ in range(FORM_REPS)]
             passed[fname] = (r, tmax, (pk, form))
@@ -1370,7 +1440,7 @@ def main():
     if region:
         how = ("one HIP event pair on the exchange stream around the timed region itself (%d back-to-back "
                "launches; launch gaps included)" % nlaunch)
-    elif not a.no_ktime:
+    elif a.full and not a.no_ktime:
         # N > 1 the region also holds RCCL: a second pass of the same K steps with an
         # event pair around every copy launch (the events cost ~7 us of device time
         # per launch, so this pass is kept out of `value`)
@@ -1432,7 +1502,8 @@ def main():
                    "ranks_per_gpu": -(-a.procs // world), "device": arch, "cus": cus,
                    "copy_variant": a.copy_variant if a.copy_variant >= 0 else int(os.environ.get("XG_COPY_VARIANT", 0)),
                    "parallelism": "block-mapped logical ranks; intra-GPU copy_kernel + grouped RCCL p2p"},
-        "max_total_time_s": max_total,      # per method, one -k repetition, median of 3 warm runs
+        # per method, one -k repetition: --full the median of 3 warm runs, else the verified (first) run's
+        "max_total_time_s": max_total,
         "roofline": roof,
         "xgmi": None,
         "pack_autotune_ms_per_run": tune or None,
@@ -1443,11 +1514,14 @@ def main():
         out["transport"] = transport()
     if cpu_cfg is not None:
         out["cpu_baseline_configs"] = cpu_cfg
-    if world > 1:
+    if a.dump_outputs:
+        phase("dump outputs")
+        dump_outputs(a.dump_outputs, runs, xg, rank, world)
+    if world > 1 and a.full:
         # N > 1: cross-GPU (xGMI) bytes of the timed region vs the measured RCCL all-pairs ceiling
         with LineGuard(out, rank, a.xgmi_budget, lambda msg: out.__setitem__("xgmi_error", msg)):
             xgmi_phase(xg, ctx, runs, world, len(methods), a.steps, elapsed, out)
-    if a.baseline_configs == "on" or (a.baseline_configs == "auto" and world == 8):
+    if baseline_configs_on(a, world):
         # BASELINE.json's 8-GPU configurations on this job, after everything above is measured.
         # The line must come out whatever happens in there: a rank still in the phase GUARD_GRACE s past
         # its budget (a peer lost inside RCCL waits forever) prints the line with what was done (rank 0)

@@ -5,7 +5,7 @@
 tag=${1:-r01}; out=$PWD/gpurun_out/prof_$tag; mkdir -p $out
 export TMPDIR=/tmp
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $out/kt -o run --output-format csv -- \
-  python3 bench.py ${BENCH_ARGS:-} > $out/bench.json 2> $out/bench.err || exit 1
+  python3 bench.py --full ${BENCH_ARGS:-} > $out/bench.json 2> $out/bench.err || exit 1
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d $out/fetch -o run --output-format csv -- \
   python3 bench.py ${BENCH_ARGS:-} --no-cpu-baseline --steps 5 --warmup 1 > /dev/null 2>&1 || exit 1
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d $out/write -o run --output-format csv -- \

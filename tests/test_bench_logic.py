@@ -44,7 +44,7 @@ def _run(world, rank, argv, tmp_path):
 
 @pytest.mark.parametrize("world", [2, 8])
 def test_bench_multi_gpu_rank0_line(world, tmp_path):
-    p = _run(world, 0, ["--gpus", str(world), "--steps", "3", "--warmup", "1", "--no-cpu-baseline"], tmp_path)
+    p = _run(world, 0, ["--gpus", str(world), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], tmp_path)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -109,7 +109,7 @@ def test_bench_multi_gpu_other_rank(tmp_path):
     with open("/tmp/xg_bench_rdzv_%s.bin" % key, "wb") as f:
         f.write(b"\x02" * 128)
     try:
-        p = _run(4, 3, ["--gpus", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], tmp_path)
+        p = _run(4, 3, ["--gpus", "4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"], tmp_path)
     finally:
         if os.path.exists("/tmp/xg_bench_rdzv_%s.bin" % key):
             os.unlink("/tmp/xg_bench_rdzv_%s.bin" % key)
@@ -128,6 +128,33 @@ def test_bench_single_gpu_line(tmp_path):
     assert out["roofline"]["avg_launch_us"] * out["roofline"]["launches_per_step"] <= out["ms_per_step"] * 1e3 * 1.001
 
 
+@pytest.mark.parametrize("world", [1, 2])
+def test_plain_run_measures_the_headline_only(world, tmp_path, monkeypatch):
+    """without --full: set-up (one verified run per plan form; at N > 1 the form choice), warm-up, the
+    timed steps, the line -- no CPU baseline, no warm max-total-time runs, no per-launch roofline pass,
+    no xGMI phase, no BASELINE configurations -- with the headline keys as in a --full line"""
+    monkeypatch.setenv("XG_FAKE_FORM_DELAY", "-1:2,0:2,1:2")     # every method's run takes 2 ms: a step ~8 ms
+    p = _run(world, 0, ["--gpus", str(world), "--steps", "3", "--warmup", "1", "--baseline-configs", "on"], tmp_path)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    assert out["metric"].startswith("aggregate exchange GB/s") and out["unit"] == "GB/s" and out["dtype"] == "u8"
+    assert out["higher_is_better"] is True and out["steps"] == 3 and out["n_gpus"] == world
+    # value = the delivered segment bytes of one step over ms_per_step
+    step_bytes = 32 * 14 * (1 << 20) * 4
+    assert out["ms_per_step"] > 0 and out["value"] == pytest.approx(step_bytes / (out["ms_per_step"] * 1e-3) / 1e9, rel=0.01)
+    assert out["cpu_baseline"] is None and out["xgmi"] is None and "baseline_configs_8gpu" not in out
+    assert set(out["max_total_time_s"]) == {"1", "2", "3", "4"}
+    calls = json.loads([l for l in p.stdout.splitlines() if l.startswith("CALLS ")][0][6:])
+    forms = 1 if world == 1 else 3
+    assert calls["p2p"] == 0 and calls["runs"] == 4 * forms           # one verified run per method and form
+    assert [k[1] for k in calls["ktime"]] == ([False] if world == 1 else [])   # N = 1: the timed region's event pair
+    p = _run(world, 0, ["--gpus", str(world), "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"], tmp_path)
+    calls = json.loads([l for l in p.stdout.splitlines() if l.startswith("CALLS ")][0][6:])
+    assert calls["runs"] == 4 * 4 * forms                               # --full: 3 more warm runs of each
+
+
 def test_watchdog_ends_a_rank_whose_peers_never_come(tmp_path):
     """rank 1 of a 2-GPU job whose rank 0 never writes the RCCL id: instead of waiting in
     the rendezvous (or, on hardware, in ncclCommInitRank) forever, the watchdog names the
@@ -144,7 +171,7 @@ def test_bench_under_torchrun_launch_form(tmp_path):
     Rank 0 prints the one JSON line, the other rank nothing, both exit 0."""
     import socket
     script = tmp_path / "bench_fake.py"
-    script.write_text(DRIVER.format(repo=REPO, argv=["--gpus", "2", "--steps", "2", "--warmup", "1",
+    script.write_text(DRIVER.format(repo=REPO, argv=["--gpus", "2", "--steps", "2", "--warmup", "1", "--full",
                                                      "--no-cpu-baseline", "--watchdog", "120"]))
     with socket.socket() as s:
         s.bind(("127.0.0.1", 0))
@@ -175,7 +202,7 @@ def _run_job(world, argv, tmp_path, extra_env):
     return [p.returncode for p in procs], outs
 
 
-ARGV2 = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--methods", "1,2"]
+ARGV2 = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--methods", "1,2"]
 
 
 def test_bench_excludes_a_form_that_fails_verification_on_one_gpu(tmp_path):
@@ -375,6 +402,9 @@ def test_wall_bound_of_the_driver_runs():
     runs both CPU phases first (the others allow for them), then watchdog + xGMI + BASELINE phases"""
     import bench
     sys.argv = ["bench.py"]
+    a = bench.parse()      # a plain run: the watchdog only, at any N
+    assert bench.wall_bound(a, 1) == bench.wall_bound(a, 2) == bench.wall_bound(a, 8) == a.watchdog == 110
+    sys.argv = ["bench.py", "--full"]
     a = bench.parse()
     assert bench.wall_bound(a, 1) == a.watchdog == 110
     b8 = bench.wall_bound(a, 8)
@@ -420,7 +450,7 @@ def test_cpu_baseline_configs_budget_and_schema(tmp_path):
 def test_link_sweep_failure_is_recorded_with_the_rccl_tail(tmp_path):
     """an RCCL error on GPU 1 in the per-link sweep's second round: every rank stops the sweep at
     that round, the line records links_error and the rounds before it, and GPU 1's RCCL warning"""
-    rcs, outs = _run_job(3, ["--gpus", "3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--methods", "1"],
+    rcs, outs = _run_job(3, ["--gpus", "3", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--methods", "1"],
                          tmp_path, {"XG_FAKE_PAIR_FAIL": "1", "XG_FAKE_FAIL_RANK": "1"})
     assert rcs == [0, 0, 0], [o[1][-1500:] for o in outs]
     out = json.loads([l for l in outs[0][0].splitlines() if l.startswith("{")][0])
@@ -433,7 +463,7 @@ def test_bench_baseline_configs_time_the_relay_form_where_it_applies(tmp_path):
     """a 4-GPU job with the BASELINE phase on: configs[3]'s pairwise m9 / m10 (permutation rounds of
     >= 1 MiB per GPU pair) are verified and timed in the direct and both relay forms and the faster is
     kept; m1 / m2 (every GPU to every GPU) have one form only"""
-    argv = ["--gpus", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--methods", "1",
+    argv = ["--gpus", "4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--methods", "1",
             "--baseline-configs", "on", "--no-ktime"]
     rcs, outs = _run_job(4, argv, tmp_path, {})
     assert rcs == [0] * 4, [o[1][-1500:] for o in outs]
@@ -498,7 +528,7 @@ def test_headline_form_choice_weighs_the_relay_form(tmp_path, delays, chosen):
     line's per-method choice times both relay forms beside direct and both packed forms, FORM_REPS times
     each (fake run times: XG_FAKE_FORM_DELAY), and keeps direct unless a form's median beats it by
     more than the spread"""
-    argv = ["--gpus", "3", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-ktime", "--procs", "16",
+    argv = ["--gpus", "3", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-ktime", "--procs", "16",
             "--aggs", "8", "--comm-size", "3", "--methods", "9"]
     rcs, outs = _run_job(3, argv, tmp_path, {"XG_FAKE_FORM_DELAY": delays})
     assert rcs == [0, 0, 0], [o[1][-1500:] for o in outs]
@@ -559,7 +589,7 @@ def test_bench_baseline_configs_drop_the_staging_that_does_not_fit(tmp_path, xg,
                     sums[k] = [max(x, y) for x, y in zip(sums[k], rb)]
     lo, hi = sum(sums[tier]), sum(sums[tier - 1])
     assert lo < hi
-    argv = ["--gpus", "4", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--methods", "1",
+    argv = ["--gpus", "4", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--methods", "1",
             "--baseline-configs", "on", "--no-ktime"]
     rcs, outs = _run_job(4, argv, tmp_path, {"XG_FAKE_REGIONS_FAIL": "%d:1" % ((lo + hi) // 2)})
     assert rcs == [0] * 4, [o[1][-1500:] for o in outs]

@@ -244,7 +244,7 @@ def test_bench_line_from_a_real_two_rank_job(tmp_path):
     xGMI (the transport is RCCL's sockets)"""
     env = _env(tmp_path)
     job = _spawn([sys.executable, "-u", os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                  "--no-cpu-baseline", "--baseline-configs", "off"], env, str(tmp_path), "bench", tmp_path)
+                  "--full", "--no-cpu-baseline", "--baseline-configs", "off"], env, str(tmp_path), "bench", tmp_path)
     (out, err), = _wait_all([job], 130)
     assert job[0].returncode == 0, err[-3000:]
     line = json.loads([x for x in out.splitlines() if x.startswith("{")][-1])
@@ -270,7 +270,7 @@ def test_bench_line_under_torchrun_launch_form(tmp_path):
     env = _env(tmp_path)
     job = _spawn([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                   "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(REPO, "bench.py"),
-                  "--gpus", "2", "--steps", "3", "--warmup", "1", "--baseline-configs", "off", "--cpu-reps", "2"],
+                  "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--baseline-configs", "off", "--cpu-reps", "2"],
                  env, str(tmp_path), "torchrun", tmp_path)
     (out, err), = _wait_all([job], 140)
     assert job[0].returncode == 0, err[-3000:]

@@ -168,7 +168,7 @@ def test_bench_ranks_issue_the_same_collectives(tmp_path, world):
     reductions, RCCL ceiling runs and plan runs, tuning passes included -- the plans it runs
     are refused up front unless their calls pair (check_pairing in MethodRun)."""
     key = "calls_%s_%s_%d" % (tmp_path.name, hashlib.sha1(str(tmp_path).encode()).hexdigest()[:10], world)
-    argv = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--watchdog", "200"]
+    argv = ["--gpus", str(world), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--watchdog", "200"]
     code = DRIVER.format(repo=REPO, argv=argv)
     procs = []
     for r in range(world):
