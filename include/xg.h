@@ -147,6 +147,11 @@ int xg_plan_engine_rails(const xg_plan *p);
 int xg_plan_engine_steps(const xg_plan *p, int *nseg, int *nhaz);
 /* Kernel launches of one run (copy + engine launches; RCCL's own kernels aside). */
 int xg_plan_launches(const xg_plan *p);
+/* Of those, the copy launches that run the wave-persistent copy_kernel_w.  *grid = the context's
+ * cap on its workgroups (occupancy x CUs; XG_WAVE_GRID, a test hook, lowers it);
+ * *max_pieces_per_wave = the largest ceil(pieces / (4 x workgroups)) over those launches, a
+ * launch of n pieces starting min(grid, ceil(n / 4)) workgroups of 4 waves.  Either may be NULL. */
+int xg_plan_wave_launches(const xg_plan *p, int *grid, int *max_pieces_per_wave);
 /* Staging displacements of the plan's packed segments as computed on the device
  * at load (one wavefront prefix scan per step and direction: the alltoallw
  * translate of mpi_test.c:233-302).  out == NULL: returns their number. */

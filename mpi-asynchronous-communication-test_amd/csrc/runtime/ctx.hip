@@ -242,6 +242,10 @@ static int init_ctx(xg_ctx *c, const void *uid)
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xgk::copy_kernel_w<xgk::kWaveKiB>, xgk::kThreads,
                                                             0));
         c->wave_grid = c->cus * (per_cu < 1 ? 1 : per_cu);
+        // test hook: a positive value caps the grid (never raises it), so that a wave gets several
+        // pieces -- on a whole device every launch of <= kWaveMax bytes has one piece per wave
+        env = getenv("XG_WAVE_GRID");
+        if (env && atoi(env) > 0) c->wave_grid = std::max(1, std::min(c->wave_grid, atoi(env)));
         // piece KiB of a wave-copy launch: 0 = by its bytes (wave_kib_for), 2 / 4 / 8 forced (A/B)
         env = getenv("XG_WAVE_KIB");
         c->wave_kib = env && (atoi(env) == 2 || atoi(env) == 4 || atoi(env) == 8) ? atoi(env) : 0;

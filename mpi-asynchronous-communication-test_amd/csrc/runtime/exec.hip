@@ -199,6 +199,47 @@ int enqueue_post(xg_plan *p, int s, hipStream_t stream)
     return XG_OK;
 }
 
+// The copy launches of one run that go to copy_kernel_w, counted dispatch by dispatch exactly as
+// enqueue_pre / enqueue_post issue them (launch_copy -> launch_cuts -> launch_one), and the
+// geometry launch_one gives them: w workgroups of 4 waves over n pieces.
+extern "C" int xg_plan_wave_launches(const xg_plan *p, int *grid, int *max_pieces_per_wave)
+{
+    int count = 0, most = 0;
+    std::vector<std::pair<int, int>> cuts;
+    auto one = [&](int b, int n, int64_t bytes, bool reread) {
+        if (n <= 0) return;
+        const int v = copy_variant(p, bytes, reread);
+        launch_cuts(p, b, n, bytes, cuts);
+        for (const auto &q : cuts) {
+            if (!(v == 1 && p->wave_at[q.first])) continue;
+            const int m = q.second - q.first;
+            const int w = std::max(1, std::min(p->ctx->wave_grid, (m + 3) / 4));
+            ++count;
+            most = std::max(most, (m + 4 * w - 1) / (4 * w));
+        }
+    };
+    for (int s = 0; s < p->nsteps; ++s) {
+        if (p->seg_of[s] >= 0) continue;        // an engine segment's step: no copy launch
+        const StepR &st = p->steps[s];
+        one(st.stage_b, st.stage_n, st.stage_bytes, true);
+        if (st.fused) {
+            const StepR &pv = p->steps[s - 1];
+            one(pv.post_b, pv.post_n + (st.fused_local ? st.local_n : 0) + st.pack_n,
+                pv.post_bytes + (st.fused_local ? st.local_bytes : 0) + st.pack_bytes, true);
+        }
+        if (st.split) {
+            if (!st.fused) one(st.pack_b, st.pack_n, st.pack_bytes, true);
+            one(st.local_b, st.local_n, st.local_bytes, false);
+        } else if (!st.fused) {
+            one(st.local_b, st.pre_n, st.local_bytes + st.pack_bytes, st.pack_n > 0 || st.stage_fused);
+        }
+        if (!st.deferred) one(st.post_b, st.post_n, st.post_bytes, false);
+    }
+    if (grid) *grid = p->ctx->wave_grid;
+    if (max_pieces_per_wave) *max_pieces_per_wave = most;
+    return count;
+}
+
 static int enqueue_step(xg_plan *p, int s)
 {
     xg_ctx *c = p->ctx;

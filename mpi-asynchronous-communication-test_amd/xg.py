@@ -570,6 +570,7 @@ def device():
         d.xg_plan_check.argtypes = [vp]
         d.xg_plan_launches.argtypes = [vp]
         d.xg_plan_engine_steps.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
+        d.xg_plan_wave_launches.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
         d.xg_plan_displs.argtypes = [vp, C.POINTER(i64), ip]
         d.xg_ktime_begin.argtypes = [vp, ip, ip]
         d.xg_ktime_end.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(ip), C.POINTER(i64)]
@@ -698,6 +699,13 @@ def now():
     return device().xg_now()
 
 
+def plan_wave_launches(plan):
+    """xg_plan_wave_launches of a loaded plan handle -> (launches, grid, max pieces per wave)"""
+    g, m = C.c_int(), C.c_int()
+    n = device().xg_plan_wave_launches(plan, C.byref(g), C.byref(m))
+    return n, g.value, m.value
+
+
 def run_virtual(runs, rccl=False):
     """Execute the MethodRuns of every GPU of one virtual job (runs[g] on Context.virtual(g, n))
     step by step on one device; returns step_done[] (device seconds).  rccl: move the
@@ -796,6 +804,10 @@ class MethodRun:
         ns, nh = C.c_int(), C.c_int()
         n = _dev.xg_plan_engine_steps(self._p, C.byref(ns), C.byref(nh))
         return n, ns.value, nh.value
+
+    def wave_launches(self):
+        """(copy launches that run copy_kernel_w, the context's wave grid, most pieces on one wave)"""
+        return plan_wave_launches(self._p)
 
     def displs(self):
         """staging displacements of the packed segments, as the device scan computed them"""

@@ -12,6 +12,8 @@ import os
 import numpy as np
 import pytest
 
+from synth_plan import Synth, _ctx_env
+
 pytestmark = pytest.mark.gpu
 
 
@@ -20,78 +22,6 @@ def ctx(xg):
     c = xg.Context(rank=0, nranks=1, device=0)
     yield c
     c.close()
-
-
-def _ctx_env(xg, **env):
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update({k: str(v) for k, v in env.items()})
-    try:
-        return xg.Context(rank=0, nranks=1, device=0)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                del os.environ[k]
-            else:
-                os.environ[k] = v
-
-
-class Synth:
-    """regions (SEND random bytes, RECV poisoned) + a synthetic one-GPU plan"""
-
-    def __init__(self, xg, ctx, send_bytes, recv_bytes, steps, seed=0):
-        d = xg.device()
-        self.xg, self.d = xg, d
-        rb = (C.c_int64 * xg.NBUF)(send_bytes, recv_bytes, 0, 0, 0)
-        self.r = C.c_void_p()
-        assert d.xg_regions_alloc(ctx.handle, rb, C.byref(self.r)) == 0
-        rng = np.random.default_rng(seed)
-        self.send = rng.integers(0, 256, send_bytes, dtype=np.uint8)
-        self.recv = np.full(recv_bytes, 0xA5, np.uint8)
-        buf = self.send.tobytes()
-        assert d.xg_regions_write(self.r, xg.BUF_SEND, 0, buf, len(buf)) == 0
-        copies = [c for st in steps for c in st]
-        self.copies = (xg.Copy * max(1, len(copies)))(
-            *[xg.Copy(so, do, ln, sb, db) for (sb, so, db, do, ln) in copies])
-        sp, b = [], 0
-        for st in steps:
-            sp.append(xg.StepPlan(b, len(st), 0, 0, 0, 0, 0, 0))
-            b += len(st)
-        self.sp = (xg.StepPlan * len(sp))(*sp)
-        self.p2p = (xg.P2P * 1)()
-        dp = xg.DevPlan()
-        dp.gpu, dp.ngpus, dp.nsteps = 0, 1, len(steps)
-        for i, v in enumerate((send_bytes, recv_bytes, 0, 0, 0)):
-            dp.region_bytes[i] = v
-        dp.ncopy, dp.np2p = len(copies), 0
-        dp.copies = C.cast(self.copies, C.POINTER(xg.Copy))
-        dp.p2p = C.cast(self.p2p, C.POINTER(xg.P2P))
-        dp.steps = C.cast(self.sp, C.POINTER(xg.StepPlan))
-        self.dp = dp
-        self.p = C.c_void_p()
-        assert d.xg_plan_load(ctx.handle, self.r, C.byref(dp), C.byref(self.p)) == 0
-        self.steps = steps
-
-    def expected(self, recv=None):
-        """RECV after one run that starts from `recv` (default: the poisoned region)"""
-        bufs = {0: self.send.copy(), 1: (self.recv if recv is None else recv).copy()}
-        for st in self.steps:
-            # one step = simultaneous copies (the generator keeps them independent)
-            vals = [bufs[sb][so:so + ln].copy() for (sb, so, db, do, ln) in st]
-            for (sb, so, db, do, ln), v in zip(st, vals):
-                bufs[db][do:do + ln] = v
-        return bufs[1]
-
-    def run(self):
-        n = max(1, len(self.steps))
-        done, post, wall = (C.c_double * n)(), (C.c_double * n)(), C.c_double()
-        assert self.d.xg_plan_run(self.p, done, post, C.byref(wall)) == 0
-        out = C.create_string_buffer(len(self.recv))
-        assert self.d.xg_regions_read(self.r, 1, 0, out, len(self.recv)) == 0
-        return np.frombuffer(out.raw, np.uint8)
-
-    def close(self):
-        self.d.xg_plan_free(self.p)
-        self.d.xg_regions_free(self.r)
 
 
 def _hazard_steps(unit, n_units, shift):

@@ -11,6 +11,20 @@ def test_known_launch_classes(xg):
     assert xg.piece_size([1 << 20] * 448, chunk=32 * K, cus=256, wg_cost=0) == 32 * K
 
 
+def test_odd_chunks_pin_the_piece_size(xg):
+    """A chunk of 16 x an odd number admits no halving (chunk / 2 is no multiple of 16), so the
+    launches of tests/test_gpu_copy_edges.py are cut into pieces of exactly that chunk on any
+    device -- each copy of at most `chunk` bytes is one piece of its own length."""
+    from synth_plan import CHUNK_A, CHUNK_B, PHASE_PAIRS, pipeline_edge_lens, realign_edge_lens
+    realign = [n for (_sp, dp) in PHASE_PAIRS for n in realign_edge_lens(dp)] + [4099, 4107]
+    for chunk, lens in ((CHUNK_A, pipeline_edge_lens(CHUNK_A)), (CHUNK_B, pipeline_edge_lens(CHUNK_B)),
+                        (CHUNK_A, realign)):
+        assert chunk % 32 == 16
+        for cus in (1, 8, 32, 64, 256, 304):
+            for cost in (0, 2048):
+                assert xg.piece_size(lens, chunk, cus, cost) == chunk, (chunk, cus, cost)
+
+
 def test_rule_against_brute_force(xg):
     import random
     rng = random.Random(5)
