@@ -62,6 +62,7 @@ int xg_init_virtual(xg_ctx **out, int rank, int nranks, int device);
 int xg_finalize(xg_ctx *ctx);
 int xg_rank(const xg_ctx *ctx);
 int xg_nranks(const xg_ctx *ctx);
+int xg_is_virtual(const xg_ctx *ctx);                           /* 1 for a context of xg_init_virtual */
 /* The self_max this context posts with (XG_SELF_MAX at xg_init, default 256 KiB): a cross-GPU
  * step whose local part moves <= this many bytes lists it as self send/recv pairs in its RCCL
  * group (xg_devplan_step_calls).  The pairing proof of a job must use the same value. */
@@ -92,6 +93,16 @@ int xg_rccl_version(int *version);
  * XG_BUF_SCRATCH (xg_devplan.region_bytes).  The RECV region is poisoned (0xA5),
  * SCRATCH is zeroed. */
 int xg_regions_alloc(xg_ctx *ctx, const int64_t region_bytes[XG_NBUF], xg_regions **out);
+/* Regions whose SEND and/or RECV are the caller's device memory (NULL: allocated here as
+ * xg_regions_alloc does); STAGE_SEND, STAGE_RECV and SCRATCH are always the library's.  An adopted
+ * pointer must be memory of the context's device, 16-B aligned, with region_bytes of it inside its
+ * allocation: XG_EARG otherwise, before anything is allocated or launched.  Nothing is written to
+ * the caller's memory here (no poison; library RECV is still poisoned, SCRATCH zeroed), and
+ * xg_regions_free frees only what the library allocated.  Every other xg_regions_* call and every
+ * plan works on adopted regions as on allocated ones; an explicit xg_regions_poison writes 0xA5
+ * over RECV whoever owns it.  The caller lays SEND and RECV out as xg_send_offset /
+ * xg_recv_offset / xg_region_bytes say. */
+int xg_regions_adopt(xg_ctx *ctx, const int64_t region_bytes[XG_NBUF], void *send, void *recv, xg_regions **out);
 int xg_regions_free(xg_regions *r);
 int xg_regions_poison(xg_regions *r);
 /* Device pointer of a region (for tests that read buffers back). */
@@ -107,6 +118,14 @@ int xg_fill(xg_regions *r, const xg_segrun *runs, int nruns, int64_t d, int iter
  * (or -1).  Any output pointer may be NULL. */
 int xg_verify(xg_regions *r, const xg_slot *slots, int nslots, int64_t d, int iter, int mode,
               uint64_t *chk, int64_t *bad, int64_t *first_bad);
+/* chk[i] = xg_chk64 of span i: `len` bytes at `off` of region `buf` (any XG_BUF_*), words counted
+ * from the span's first byte -- bytes whose contents the library need not know (a caller's
+ * payload).  Any lengths (0 included) and start alignments, one kernel launch for all of them.
+ * The kernel reads whole aligned 16-B granules: of memory outside a span, only the rest of the
+ * granules holding its first and last byte.  XG_EARG for a span outside its region or a launch
+ * of more than 2^31 - 1 workgroups (one per 64 KiB of a span); n == 0 is XG_OK. */
+typedef struct { int32_t buf, pad; int64_t off, len; } xg_bufspan;
+int xg_chk_spans(xg_regions *r, const xg_bufspan *spans, int n, uint64_t *chk);
 
 /* ------------------------------------------------------------------ plans */
 int xg_plan_load(xg_ctx *ctx, xg_regions *r, const xg_devplan *dp, xg_plan **out);
@@ -243,6 +262,19 @@ void xg_run_opts_default(xg_run_opts *o);
 int xg_run_method(xg_ctx *ctx, int method, int procs, int cb_nodes, int data_size, const int *rank_list,
                   int comm_size, xg_timer *timers, int iter, int ntimes, const xg_run_opts *opts,
                   int64_t *bad_slots, char *err, size_t errlen);
+
+/* The same exchange over the CALLER's device buffers (exchange.c): send / recv are this GPU's SEND
+ * and RECV regions (xg_regions_adopt's rules; NULL: allocated here), laid out as xg_send_offset /
+ * xg_recv_offset / xg_region_bytes say for the schedule of these arguments.  Same schedule, plan
+ * and kernels as xg_run_method; nothing is filled (opts->fingerprint is ignored) and SEND is only
+ * read.  opts->verify: delivery is checked end to end by xg_chk_spans -- every send segment's
+ * checksum before the run, shared over the job, against its receive slot's afterwards
+ * (xg_deliveries); *bad_slots = this GPU's slots that differ.  XG_EARG for a virtual context.  A
+ * rank whose buffers are refused fails the call on every rank alike before the exchange's first
+ * RCCL call. */
+int xg_exchange(xg_ctx *ctx, int method, int procs, int cb_nodes, int data_size, const int *rank_list,
+                int comm_size, void *send, void *recv, xg_timer *timers, int iter, int ntimes,
+                const xg_run_opts *opts, int64_t *bad_slots, char *err, size_t errlen);
 
 /* The operators under the reference's names (mpi_test.c line of the original). */
 #define XG_METHOD_DECL(name)                                                                     \

@@ -371,6 +371,14 @@ enum { XG_FP_REFERENCE = 0, XG_FP_STRONG = 1 };   /* fingerprint modes (DESIGN.m
 int xg_fill_runs(const xg_sched *s, int ngpus, int g, xg_segrun *out);
 int xg_verify_slots(const xg_sched *s, int ngpus, int g, xg_slot *out);
 
+/* Every receive slot of the job and the send segment it must equal after the run (any method
+ * 1..20, TAM included: what check_buffer's call sites :139 / :215 pair), whatever the bytes are:
+ * slot `slot` of rank dst, at recv_off in dst_gpu's RECV, holds the d bytes at send_off =
+ * xg_send_offset(src) + seed * d of src_gpu's SEND.  Ordered by (dst_gpu, xg_verify_slots order).
+ * Returns the count; out may be NULL to query it. */
+typedef struct { int32_t src, seed, dst, slot, src_gpu, dst_gpu; int64_t send_off, recv_off; } xg_delivery;
+int xg_deliveries(const xg_sched *s, int ngpus, xg_delivery *out);
+
 /* save_all_timing (mpi_test.c:2008-2066): the four per-repetition CSVs of m13,
  * <prefix>send_wait_all_times_<c>.csv, total_times, post_request_time,
  * barrier_time; timers = procs x ntimes, rank-major. */

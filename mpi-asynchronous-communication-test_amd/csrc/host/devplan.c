@@ -1063,3 +1063,28 @@ int xg_verify_slots(const xg_sched *s, int ngpus, int g, xg_slot *out)
     }
     return n;
 }
+
+int xg_deliveries(const xg_sched *s, int ngpus, xg_delivery *out)
+{
+    int g, lo, hi, r, i, n = 0;
+    for (g = 0; g < ngpus; ++g) {
+        xg_block_range(s->P, ngpus, g, &lo, &hi);
+        for (r = lo; r < hi; ++r) {          /* xg_verify_slots' order and pairing */
+            int nslots = xgi_nrecv_slots(s, r), myindex = 0;
+            if (!nslots) continue;
+            for (i = 0; i < s->A; ++i)
+                if (s->rank_list[i] == r) myindex = i;
+            for (i = 0; i < nslots; ++i, ++n) {
+                xg_delivery *q = out ? &out[n] : NULL;
+                if (!q) continue;
+                q->src = s->dir == XG_A2M ? i : s->rank_list[i];
+                q->seed = s->dir == XG_A2M ? myindex : r;
+                q->dst = r; q->slot = i;
+                q->src_gpu = xg_gpu_of(s->P, ngpus, q->src); q->dst_gpu = g;
+                q->send_off = xg_send_offset(s, ngpus, q->src) + (int64_t)q->seed * s->d;
+                q->recv_off = xg_recv_offset(s, ngpus, r) + (int64_t)i * s->d;
+            }
+        }
+    }
+    return n;
+}

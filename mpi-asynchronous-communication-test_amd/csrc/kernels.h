@@ -999,4 +999,122 @@ __device__ __forceinline__ uint64_t wave_min(uint64_t v)
     }
 }
 
+// ---------------------------------------------------------------- span checksum
+// xg_chk64 (without its length term, added on the host) of n spans of any length and any start
+// alignment, in one launch: bytes whose contents the library does not know (a caller's payload),
+// so there is nothing to compare with -- a pure HBM read.  Span i owns workgroups blk0 .. of the
+// grid, one per kChkChunk bytes of it (an empty span owns none); a workgroup finds its span by a
+// binary search over blk0 (uniform: scalar loads).  Words are counted from the span's first byte.
+//
+// Loads are whole ALIGNED 16-B granules through a buffer resource that ends with the granule
+// holding the span's last byte, so nothing outside the granules of its first and last byte is
+// read and a short last batch needs no branch.  A span that starts at phase ph != 0 of a granule
+// loads the two granules each of its 16-B pieces straddles (the second is the next lane's first:
+// an L1 hit) and funnel-shifts them (v_alignbyte) -- no byte loop anywhere; the bytes of the last
+// word past the span's end are masked off.  Per lane U loads (2U when shifted) are in flight.
+constexpr int kChkChunk = 65536;        // bytes of a span per workgroup (a multiple of 16)
+constexpr int kChkU = 4;
+
+struct DSpan {
+    const uint8_t *p;
+    int64_t len;
+    int64_t blk0;       // first workgroup of the span; nondecreasing, blk0[n] would be the grid
+};
+
+__device__ __forceinline__ uint64_t u64of(uint32_t lo, uint32_t hi) { return ((uint64_t)hi << 32) | lo; }
+
+// bytes [ph, ph + 16) of the 32-byte window {a, b}; ph (1..15) is uniform in the workgroup
+__device__ __forceinline__ u32x4 shift_window(u32x4 a, u32x4 b, int ph)
+{
+    const bool s2 = ph & 8, s1 = ph & 4;
+    const uint32_t e0 = s2 ? a.z : a.x, e1 = s2 ? a.w : a.y, e2 = s2 ? b.x : a.z, e3 = s2 ? b.y : a.w,
+                   e4 = s2 ? b.z : b.x, e5 = s2 ? b.w : b.y;
+    const uint32_t f0 = s1 ? e1 : e0, f1 = s1 ? e2 : e1, f2 = s1 ? e3 : e2, f3 = s1 ? e4 : e3, f4 = s1 ? e5 : e4;
+    const int sh = ph & 3;
+    u32x4 v;
+    v.x = __builtin_amdgcn_alignbyte(f1, f0, sh);
+    v.y = __builtin_amdgcn_alignbyte(f2, f1, sh);
+    v.z = __builtin_amdgcn_alignbyte(f3, f2, sh);
+    v.w = __builtin_amdgcn_alignbyte(f4, f3, sh);
+    return v;
+}
+
+// the two words of one whole 16-B piece; key = (index of its first word) * kGold
+__device__ __forceinline__ uint64_t chk_piece(u32x4 v, uint64_t key)
+{
+    return mix64(u64of(v.x, v.y) ^ key) + mix64(u64of(v.z, v.w) ^ (key + kGold));
+}
+
+template <bool SHIFT>
+__device__ __forceinline__ uint64_t chk_chunk(brsrc rs, int ph, int nfull, int rem, uint64_t key0)
+{
+    constexpr int U = kChkU;
+    uint64_t sum = 0;
+    int j = (int)threadIdx.x;
+    uint64_t key = key0 + (uint64_t)(2 * j) * kGold;
+    const uint64_t kstep = (uint64_t)(2 * kThreads) * kGold;
+    for (; j + (U - 1) * kThreads < nfull; j += U * kThreads) {
+        u32x4 a[U], b[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            a[u] = bload16(rs, (j + u * kThreads) * 16);
+            if constexpr (SHIFT) b[u] = bload16(rs, (j + u * kThreads) * 16 + 16);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            sum += chk_piece(SHIFT ? shift_window(a[u], b[u], ph) : a[u], key);
+            key += kstep;
+        }
+    }
+    for (; j < nfull; j += kThreads) {
+        u32x4 a = bload16(rs, j * 16);
+        if constexpr (SHIFT) a = shift_window(a, bload16(rs, j * 16 + 16), ph);
+        sum += chk_piece(a, key);
+        key += kstep;
+    }
+    if (rem && j == nfull) {          // the span's last piece, 1..15 bytes: exactly one lane gets here with j == nfull
+        u32x4 a = bload16(rs, j * 16);
+        if constexpr (SHIFT) a = shift_window(a, bload16(rs, j * 16 + 16), ph);   // past the last granule: reads 0
+        const uint64_t w0 = u64of(a.x, a.y), w1 = u64of(a.z, a.w);
+        if (rem > 8) sum += mix64(w0 ^ key) + mix64((w1 & ((1ull << (8 * (rem - 8))) - 1)) ^ (key + kGold));
+        else sum += mix64((rem < 8 ? w0 & ((1ull << (8 * rem)) - 1) : w0) ^ key);
+    }
+    return sum;
+}
+
+[[maybe_unused]] static __global__ __launch_bounds__(kThreads) void span_chk_kernel(const DSpan *__restrict__ spans, int n,
+                                                            unsigned long long *chk)
+{
+    __shared__ uint64_t wsum[kThreads / 64];
+    const int64_t b = blockIdx.x;
+    int lo = 0, hi = n - 1;                       // the last span with blk0 <= b (never an empty one)
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (spans[mid].blk0 <= b) lo = mid;
+        else hi = mid - 1;
+    }
+    const DSpan sp = spans[lo];
+    const int64_t c0 = (b - sp.blk0) * kChkChunk;
+    const int64_t left = sp.len - c0;             // > 0
+    const int clen = left < kChkChunk ? (int)left : kChkChunk;
+    const int ph = (int)((uintptr_t)sp.p & 15);
+    // aligned granules from the one holding the chunk's first byte to the one holding its last,
+    // plus (shifted) the one its last whole piece runs into: all inside the span's own granules
+    const int64_t span_end = (ph + sp.len + 15) & ~(int64_t)15;
+    const int64_t recs = span_end - c0 < kChkChunk + 16 ? span_end - c0 : kChkChunk + 16;
+    const brsrc rs = make_rsrc(sp.p - ph + c0, recs);
+    const uint64_t key0 = (uint64_t)(c0 >> 3) * kGold;
+    uint64_t sum = ph ? chk_chunk<true>(rs, ph, clen >> 4, clen & 15, key0)
+                      : chk_chunk<false>(rs, 0, clen >> 4, clen & 15, key0);
+    sum = wave_sum(sum);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint64_t t = 0;
+#pragma unroll
+        for (int w = 0; w < kThreads / 64; ++w) t += wsum[w];
+        atomicAdd(&chk[lo], (unsigned long long)t);
+    }
+}
+
 }  // namespace xgk

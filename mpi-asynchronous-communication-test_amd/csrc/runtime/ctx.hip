@@ -412,26 +412,78 @@ extern "C" int xg_set_copy_params(xg_ctx *c, int64_t chunk, int variant)
 }
 
 // ------------------------------------------------------------------ regions
-extern "C" int xg_regions_alloc(xg_ctx *c, const int64_t bytes[XG_NBUF], xg_regions **out)
+// the caller's device pointer p for a region of `bytes`: on this context's device, 16-B aligned (the
+// copy kernels' aligned path and RCCL), and the region inside the allocation p points into
+static int adoptable(const xg_ctx *c, const void *p, int64_t bytes, const char *what)
 {
+    hipPointerAttribute_t at;
+    void *base = nullptr;
+    size_t size = 0;
+    if ((uintptr_t)p & 15) {
+        fprintf(stderr, "xg_regions_adopt: the %s pointer %p is not 16-byte aligned\n", what, p);
+        return XG_EARG;
+    }
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->device) {
+        (void)hipGetLastError();
+        fprintf(stderr, "xg_regions_adopt: the %s pointer %p is not device memory of device %d\n", what, p, c->device);
+        return XG_EARG;
+    }
+    if (hipMemGetAddressRange((hipDeviceptr_t *)&base, &size, (hipDeviceptr_t)p) != hipSuccess ||
+        (const uint8_t *)p + bytes > (const uint8_t *)base + size) {
+        (void)hipGetLastError();
+        fprintf(stderr, "xg_regions_adopt: the %s region of %lld bytes at %p does not fit its allocation\n", what,
+                (long long)bytes, p);
+        return XG_EARG;
+    }
+    return XG_OK;
+}
+
+// at creation: poison / zero what the library allocated, never the caller's memory
+static int poison_regions(xg_regions *r, bool owned_only)
+{
+    if (r->bytes[XG_BUF_RECV] > 0 && (r->owned[XG_BUF_RECV] || !owned_only))
+        HIPCHK(hipMemsetAsync(r->ptr[XG_BUF_RECV], 0xA5, (size_t)r->bytes[XG_BUF_RECV], r->ctx->stream));
+    if (r->bytes[XG_BUF_SCRATCH] > 0)   /* TAM aggregation buffers start zeroed (gaps stay deterministic) */
+        HIPCHK(hipMemsetAsync(r->ptr[XG_BUF_SCRATCH], 0, (size_t)r->bytes[XG_BUF_SCRATCH], r->ctx->stream));
+    HIPCHK(hipStreamSynchronize(r->ctx->stream));
+    return XG_OK;
+}
+
+extern "C" int xg_regions_adopt(xg_ctx *c, const int64_t bytes[XG_NBUF], void *send, void *recv, xg_regions **out)
+{
+    if (!c || !bytes || !out) return XG_EARG;
     HIPCHK(hipSetDevice(c->device));
+    void *const theirs[XG_NBUF] = {send, recv, nullptr, nullptr, nullptr};
+    static const char *const names[XG_NBUF] = {"SEND", "RECV", "", "", ""};
+    for (int i = 0; i < XG_NBUF; ++i) {
+        if (bytes[i] < 0) return XG_EARG;
+        if (theirs[i] && bytes[i] > 0 && adoptable(c, theirs[i], bytes[i], names[i])) return XG_EARG;
+    }
     xg_regions *r = new xg_regions();
     r->ctx = c;
     for (int i = 0; i < XG_NBUF; ++i) {
         r->bytes[i] = bytes[i];
         r->ptr[i] = nullptr;
-        if (bytes[i] > 0) {
-            hipError_t e = hipMalloc(&r->ptr[i], (size_t)bytes[i]);
-            if (e != hipSuccess) {
-                fprintf(stderr, "xg: hipMalloc(%lld) for region %d failed: %s\n", (long long)bytes[i], i,
-                        hipGetErrorString(e));
-                for (int j = 0; j < i; ++j) (void)hipFree(r->ptr[j]);
-                delete r;
-                return XG_ENOMEM;
-            }
-        }
+        r->owned[i] = false;
     }
-    const int rc = xg_regions_poison(r);
+    for (int i = 0; i < XG_NBUF; ++i) {
+        if (bytes[i] <= 0) continue;
+        if (theirs[i]) {
+            r->ptr[i] = static_cast<uint8_t *>(theirs[i]);
+            continue;
+        }
+        hipError_t e = hipMalloc(&r->ptr[i], (size_t)bytes[i]);
+        if (e != hipSuccess) {
+            fprintf(stderr, "xg: hipMalloc(%lld) for region %d failed: %s\n", (long long)bytes[i], i,
+                    hipGetErrorString(e));
+            (void)hipGetLastError();
+            r->ptr[i] = nullptr;
+            (void)xg_regions_free(r);
+            return XG_ENOMEM;
+        }
+        r->owned[i] = true;
+    }
+    const int rc = poison_regions(r, true);
     if (rc) {                     /* nothing half made is handed out */
         (void)xg_regions_free(r);
         return rc;
@@ -440,22 +492,19 @@ extern "C" int xg_regions_alloc(xg_ctx *c, const int64_t bytes[XG_NBUF], xg_regi
     return XG_OK;
 }
 
-extern "C" int xg_regions_poison(xg_regions *r)
+extern "C" int xg_regions_alloc(xg_ctx *c, const int64_t bytes[XG_NBUF], xg_regions **out)
 {
-    if (r->bytes[XG_BUF_RECV] > 0)
-        HIPCHK(hipMemsetAsync(r->ptr[XG_BUF_RECV], 0xA5, (size_t)r->bytes[XG_BUF_RECV], r->ctx->stream));
-    if (r->bytes[XG_BUF_SCRATCH] > 0)   /* TAM aggregation buffers start zeroed (gaps stay deterministic) */
-        HIPCHK(hipMemsetAsync(r->ptr[XG_BUF_SCRATCH], 0, (size_t)r->bytes[XG_BUF_SCRATCH], r->ctx->stream));
-    HIPCHK(hipStreamSynchronize(r->ctx->stream));
-    return XG_OK;
+    return xg_regions_adopt(c, bytes, nullptr, nullptr, out);
 }
+
+extern "C" int xg_regions_poison(xg_regions *r) { return poison_regions(r, false); }
 
 extern "C" int xg_regions_free(xg_regions *r)
 {
     if (!r) return XG_OK;
     HIPCHK(hipStreamSynchronize(r->ctx->stream));
     for (int i = 0; i < XG_NBUF; ++i)
-        if (r->ptr[i]) HIPCHK(hipFree(r->ptr[i]));
+        if (r->ptr[i] && r->owned[i]) HIPCHK(hipFree(r->ptr[i]));
     delete r;
     return XG_OK;
 }
@@ -548,3 +597,43 @@ extern "C" int xg_verify(xg_regions *r, const xg_slot *slots, int nslots, int64_
     return XG_OK;
 }
 
+// xg_chk64 of every span (include/xg.h): one span_chk_kernel launch over all of them
+extern "C" int xg_chk_spans(xg_regions *r, const xg_bufspan *spans, int n, uint64_t *chk)
+{
+    if (!r || n < 0 || (n > 0 && (!spans || !chk))) return XG_EARG;
+    if (n == 0) return XG_OK;
+    xg_ctx *c = r->ctx;
+    std::vector<xgk::DSpan> ds(n);
+    int64_t blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const xg_bufspan &s = spans[i];
+        if (s.buf < 0 || s.buf >= XG_NBUF || s.off < 0 || s.len < 0 || s.off > r->bytes[s.buf] ||
+            s.len > r->bytes[s.buf] - s.off)
+            return XG_EARG;
+        ds[i].p = r->ptr[s.buf] + s.off;
+        ds[i].len = s.len;
+        ds[i].blk0 = blocks;
+        blocks += (s.len + xgk::kChkChunk - 1) / xgk::kChkChunk;
+        if (blocks > 0x7fffffff) return XG_EARG;
+    }
+    std::vector<unsigned long long> h(n, 0);
+    if (blocks > 0) {
+        HIPCHK(hipSetDevice(c->device));
+        DevMem m_sp, m_out;
+        HIPCHK(hipMalloc(&m_sp.p, sizeof(xgk::DSpan) * n));
+        HIPCHK(hipMalloc(&m_out.p, sizeof(unsigned long long) * n));
+        xgk::DSpan *dsp = m_sp.as<xgk::DSpan>();
+        unsigned long long *dout = m_out.as<unsigned long long>();
+        HIPCHK(hipMemcpyAsync(dsp, ds.data(), sizeof(xgk::DSpan) * n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemsetAsync(dout, 0, sizeof(unsigned long long) * n, c->stream));
+        hipLaunchKernelGGL(xgk::span_chk_kernel, dim3((unsigned)blocks), dim3(xgk::kThreads), 0, c->stream, dsp, n,
+                           dout);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(h.data(), dout, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    for (int i = 0; i < n; ++i) chk[i] = h[i] + 0xD6E8FEB86659FD93ull * (uint64_t)spans[i].len;
+    return XG_OK;
+}
+
+extern "C" int xg_is_virtual(const xg_ctx *c) { return c && c->virt ? 1 : 0; }

@@ -2,7 +2,7 @@
 // context, region and plan structures every runtime translation unit shares, the error
 // macros, and the helpers more than one of them calls.  gfx950 only.
 //
-//   ctx.hip        context (streams, communicator), HBM regions, fill / verify
+//   ctx.hip        context (streams, communicator), HBM regions, fill / verify / span checksums
 //   plan_load.hip  xg_plan_load: piece table, launch forms, engine segments, displacement scan
 //   exec.hip       execution: per-step launches + RCCL groups, chains, engine, graph, armed runs
 //   virtual.hip    a whole G-GPU job on one device (test hook)
@@ -156,6 +156,7 @@ struct xg_regions {
     xg_ctx *ctx;
     uint8_t *ptr[XG_NBUF];
     int64_t bytes[XG_NBUF];
+    bool owned[XG_NBUF];    // hipMalloc'd here (freed, poisoned at creation); false: the caller's memory (xg_regions_adopt)
 };
 
 struct StepR {

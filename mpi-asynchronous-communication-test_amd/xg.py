@@ -92,6 +92,25 @@ class Slot(C.Structure):
                 ("off", C.c_int64)]
 
 
+class Delivery(C.Structure):
+    """xg_delivery: receive slot `slot` of rank dst (recv_off in dst_gpu's RECV) must equal the
+    segment at send_off of src_gpu's SEND."""
+    _fields_ = [("src", C.c_int32), ("seed", C.c_int32), ("dst", C.c_int32), ("slot", C.c_int32),
+                ("src_gpu", C.c_int32), ("dst_gpu", C.c_int32), ("send_off", C.c_int64), ("recv_off", C.c_int64)]
+
+
+class BufSpan(C.Structure):
+    """xg_bufspan: len bytes at off of region buf"""
+    _fields_ = [("buf", C.c_int32), ("pad", C.c_int32), ("off", C.c_int64), ("len", C.c_int64)]
+
+
+class RunOpts(C.Structure):
+    """xg_run_opts"""
+    _fields_ = [("verify", C.c_int), ("fingerprint", C.c_int), ("eager_limit", C.c_int64),
+                ("pack_max_seg", C.c_int64), ("proc_node", C.c_int), ("barrier_type", C.c_int),
+                ("rep_timers", C.POINTER(Timer)), ("pack_min_bytes", C.c_int64), ("pack_form", C.c_int)]
+
+
 A2M, M2A = 0, 1
 BUF_SEND, BUF_RECV, BUF_STAGE_SEND, BUF_STAGE_RECV, BUF_SCRATCH = 0, 1, 2, 3, 4
 PACK_TWO_SIDED, PACK_ONE_SIDED, RELAY, RELAY_COALESCED = 0, 1, 2, 3   # xg_devplan_build_form (xg_sched.h XG_RELAY, XG_RELAY_COALESCED)
@@ -169,6 +188,7 @@ def host():
         h.xg_piece_size.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_int, C.c_int64]
         h.xg_fill_runs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SegRun)]
         h.xg_verify_slots.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Slot)]
+        h.xg_deliveries.argtypes = [C.c_void_p, C.c_int, C.POINTER(Delivery)]
         h.xg_engine_hazards.argtypes = [C.POINTER(Span), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int)]
         h.xg_solo_reduce_stamps.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int64, C.c_int, C.c_int,
                                             C.POINTER(C.c_uint64)]
@@ -432,6 +452,14 @@ class Schedule:
         host().xg_verify_slots(self._h, ngpus, g, sl)
         return [(x.src, x.seed, x.dst, x.off) for x in sl[:n]]
 
+    def deliveries(self, ngpus):
+        """xg_deliveries: every receive slot of the job with the send segment it must equal, as
+        Delivery records (src, seed, dst, slot, src_gpu, dst_gpu, send_off, recv_off)"""
+        n = host().xg_deliveries(self._h, ngpus, None)
+        out = (Delivery * max(1, n))()
+        host().xg_deliveries(self._h, ngpus, out)
+        return list(out[:n])
+
 
 class DevicePlanView:
     """Python view of xg_devplan (host memory), used by the CPU plan tests."""
@@ -551,6 +579,13 @@ def device():
         d.xg_device_info.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(ip), C.POINTER(C.c_size_t)]
         d.xg_now.restype = C.c_double
         d.xg_regions_alloc.argtypes = [vp, C.POINTER(i64), C.POINTER(vp)]
+        d.xg_regions_adopt.argtypes = [vp, C.POINTER(i64), vp, vp, C.POINTER(vp)]
+        d.xg_chk_spans.argtypes = [vp, C.POINTER(BufSpan), ip, C.POINTER(C.c_uint64)]
+        d.xg_is_virtual.argtypes = [vp]
+        d.xg_run_opts_default.argtypes = [C.POINTER(RunOpts)]
+        d.xg_run_opts_default.restype = None
+        d.xg_exchange.argtypes = [vp, ip, ip, ip, ip, C.POINTER(ip), ip, vp, vp, C.POINTER(Timer), ip, ip,
+                                  C.POINTER(RunOpts), C.POINTER(i64), C.c_char_p, C.c_size_t]
         d.xg_regions_free.argtypes = [vp]
         d.xg_regions_poison.argtypes = [vp]
         d.xg_regions_ptr.restype = vp
@@ -730,8 +765,34 @@ class Regions:
         self._r = C.c_void_p()
         _check(device().xg_regions_alloc(ctx.handle, rb, C.byref(self._r)), "xg_regions_alloc")
 
+    @classmethod
+    def adopt(cls, ctx, region_bytes, send=None, recv=None):
+        """Regions whose SEND / RECV are the caller's device memory (addresses as int; None:
+        allocated here): xg_regions_adopt.  Nothing is written to adopted memory, close() frees
+        only what the library allocated."""
+        self = cls.__new__(cls)
+        self.bytes = list(region_bytes)
+        rb = (C.c_int64 * NBUF)(*self.bytes)
+        self._r = C.c_void_p()
+        _check(device().xg_regions_adopt(ctx.handle, rb, C.c_void_p(send), C.c_void_p(recv), C.byref(self._r)),
+               "xg_regions_adopt")
+        return self
+
     def fits(self, region_bytes):
         return all(a <= b for a, b in zip(region_bytes, self.bytes))
+
+    def ptr(self, buf):
+        """device address of a region (int; 0 for an empty one)"""
+        return _dev.xg_regions_ptr(self._r, buf) or 0
+
+    def read(self, buf, off, length):
+        out = C.create_string_buffer(max(1, length))
+        _check(_dev.xg_regions_read(self._r, buf, off, out, length), "xg_regions_read")
+        return out.raw[:length]
+
+    def write(self, buf, off, data):
+        b = C.create_string_buffer(bytes(data), len(data))
+        _check(_dev.xg_regions_write(self._r, buf, off, b, len(data)), "xg_regions_write")
 
     def close(self):
         if getattr(self, "_r", None):
@@ -739,12 +800,66 @@ class Regions:
             self._r = None
 
 
+def chk_spans(regions_or_run, spans):
+    """xg_chk_spans: xg_chk64 of every (buf, off, len) span of a Regions' or MethodRun's regions,
+    in one kernel launch"""
+    n = len(spans)
+    arr = (BufSpan * max(1, n))(*[BufSpan(b, 0, o, ln) for b, o, ln in spans])
+    out = (C.c_uint64 * max(1, n))()
+    _check(device().xg_chk_spans(regions_or_run._r, arr, n, out), "xg_chk_spans")
+    return list(out)[:n]
+
+
+def payload_check(runs):
+    """The runs of one job (a MethodRun, or the G runs of a virtual job, in GPU order) after its
+    exchange: every receive slot's checksum against its source segment's in the owning run's
+    SEND (Schedule.deliveries) -- bytes the library need not know.  Returns the bad (dst, slot)."""
+    runs = [runs] if isinstance(runs, MethodRun) else list(runs)
+    G, d = len(runs), runs[0].sched.d
+    dl = runs[0].sched.deliveries(G)
+    src, dst = [None] * len(dl), [None] * len(dl)
+    for g, run in enumerate(runs):
+        ks = [k for k, q in enumerate(dl) if q.src_gpu == g]
+        for k, c in zip(ks, chk_spans(run, [(BUF_SEND, dl[k].send_off, d) for k in ks])):
+            src[k] = c
+        kr = [k for k, q in enumerate(dl) if q.dst_gpu == g]
+        for k, c in zip(kr, chk_spans(run, [(BUF_RECV, dl[k].recv_off, d) for k in kr])):
+            dst[k] = c
+    return [(q.dst, q.slot) for k, q in enumerate(dl) if src[k] != dst[k]]
+
+
+def exchange(ctx, method, procs, cb_nodes, data_size, rank_list, comm_size, send, recv, it=0, ntimes=1,
+             verify=True, proc_node=1, pack_form=-1):
+    """xg_exchange: the method's exchange over the caller's device buffers (addresses as int, laid
+    out as Schedule.send_offset / recv_offset / region_bytes say).  Returns (rc, bad_slots,
+    [Timer of every hosted rank], error text); raises nothing, so that every rank of a job sees
+    the code."""
+    d = device()
+    o = RunOpts()
+    d.xg_run_opts_default(C.byref(o))
+    o.verify, o.proc_node = 1 if verify else 0, proc_node
+    if pack_form >= 0:
+        o.pack_form = pack_form
+    lo, hi = C.c_int(), C.c_int()
+    host().xg_block_range(procs, ctx.nranks, ctx.rank, C.byref(lo), C.byref(hi))
+    timers = (Timer * max(1, hi.value - lo.value))()
+    rl = (C.c_int * cb_nodes)(*rank_list)
+    bad = C.c_int64()
+    err = C.create_string_buffer(512)
+    rc = d.xg_exchange(ctx.handle, method, procs, cb_nodes, data_size, rl, comm_size, C.c_void_p(send),
+                       C.c_void_p(recv), timers, it, ntimes, C.byref(o), C.byref(bad), err, 512)
+    return rc, bad.value, list(timers)[:hi.value - lo.value], err.value.decode()
+
+
 class MethodRun:
     """prepare_*_data + the compiled plan of one method on this GPU:
     HBM regions, fingerprint fill (untimed), plan upload.  regions: a Regions
-    object to use (re-poisoned here, not freed by close()) instead of new ones."""
+    object to use (re-poisoned here, not freed by close()) instead of new ones.
+    fill=False: SEND keeps what it holds (a caller's payload, written with write() or adopted
+    with Regions.adopt); check delivery with payload_check()."""
 
-    def __init__(self, ctx, sched, it=0, mode=0, pack_max_seg=4 << 20, regions=None, pack_min=0, pack_form=-1):
+    def __init__(self, ctx, sched, it=0, mode=0, pack_max_seg=4 << 20, regions=None, pack_min=0, pack_form=-1,
+                 fill=True):
         d = device()
         self.ctx, self.sched, self.it, self.mode, self.pack_max_seg = ctx, sched, it, mode, pack_max_seg
         self.pack_min, self.pack_form = pack_min, pack_form
@@ -767,7 +882,8 @@ class MethodRun:
         n = host().xg_fill_runs(sched.handle, G, g, None)
         runs = (SegRun * max(1, n))()
         host().xg_fill_runs(sched.handle, G, g, runs)
-        _check(d.xg_fill(self._r, runs, n, sched.d, it, mode), "xg_fill")
+        if fill:
+            _check(d.xg_fill(self._r, runs, n, sched.d, it, mode), "xg_fill")
         ns = host().xg_verify_slots(sched.handle, G, g, None)
         self._slots = (Slot * max(1, ns))()
         host().xg_verify_slots(sched.handle, G, g, self._slots)
@@ -841,6 +957,11 @@ class MethodRun:
         _check(_dev.xg_verify(self._r, self._slots, self.nslots, self.sched.d, self.it, self.mode,
                               chk, bad, first), "xg_verify")
         return list(chk)[:self.nslots], list(bad)[:self.nslots], list(first)[:self.nslots]
+
+    def slot_chk(self):
+        """xg_chk64 of every receive slot (self.slots order) by xg_chk_spans -- no fingerprint
+        needed; equals verify()[0]"""
+        return chk_spans(self, [(BUF_RECV, off, self.sched.d) for _s, _e, _d, off in self.slots])
 
     def read(self, buf, off, length):
         out = C.create_string_buffer(max(1, length))
