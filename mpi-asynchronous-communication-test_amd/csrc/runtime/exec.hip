@@ -1,5 +1,6 @@
-// exec.hip -- execution of a loaded plan: per-step copy launches and RCCL groups, chains of
-// stamped launches, engine segments, graph replay, armed (doorbell) runs, step marks.
+// exec.hip -- execution of a loaded plan: each step's entries of the plan's launch table and its
+// RCCL groups, chains of stamped launches, engine segments, graph replay, armed (doorbell)
+// runs, step marks.  Nothing here decides how a step's copies launch: xg_plan_load did.
 #include "rt.h"
 
 extern "C" const char *xg_debug_where(void)
@@ -10,11 +11,11 @@ extern "C" const char *xg_debug_where(void)
 }
 
 // Execution of one step on GPU g (xg_devplan, built by libxghost):
-//   1. one copy_kernel launch over every local gather/scatter piece and every
-//      pack into the per-peer staging region                (pre copies)
+//   1. the step's launch-table entries up to its RCCL group: stage copies, local
+//      gather/scatter, packs into the per-peer staging region (pre copies)
 //   2. one ncclGroupStart .. ncclSend/ncclRecv .. ncclGroupEnd with the <= 7
 //      peer GPUs this step talks to (xGMI)                  (p2p)
-//   3. one copy_kernel launch unpacking staging into the receive slots (post)
+//   3. the entries behind it: staging unpacked into the receive slots (post)
 //   4. a clock_kernel stamp (step mark) -- the reference's Waitall boundary
 // All on one HIP stream per context, so step s+1 starts after step s; the
 // cross-GPU order comes from RCCL send/recv matching.
@@ -41,59 +42,28 @@ double mark_elapsed(const xg_plan *p, int i, const std::vector<unsigned long lon
     return (double)(gs[i + 1] - gs[0]) / p->ctx->wall_hz;
 }
 
-// Copy kernel per launch.  Variant 0 (default) picks by the launch's bytes: a launch
-// whose source + destination exceed the 256 MiB Infinity Cache streams through it with
-// non-temporal loads and stores (6.3 TB/s vs 5.5-5.6 plain from 256 MiB up), a smaller
-// one keeps the default policy, which re-runs serve from the cache
-// (profiles/r02/copy_nt_sizes.txt).  1 / 6 force one form (A/B, tests).
-//
-// A launch of more than 1.5 x launch_max bytes goes as back-to-back kernel dispatches of
-// about launch_max bytes each (its pieces are independent: the same step, a few more
-// kernel boundaries).  P256 A32 -d 4 MiB m1 / m2 (one 32 GiB step, 1 M pieces): 12.6 ->
-// 11.0 ms at 512 MiB per dispatch, 11.5 at 128 MiB; cutting by piece count instead hurt
-// steps of small pieces (profiles/r02/launch_split/).  launch_cuts gives the dispatches
-// [first piece, end) of pieces [b, b + n): every count of launches (xg_plan_launches, the
-// kernel-timing sessions) counts these dispatches, as rocprofv3 does.
-static void launch_cuts(const xg_plan *p, int b, int n, int64_t bytes, std::vector<std::pair<int, int>> &out)
-{
-    out.clear();
-    const int64_t cap = p->ctx->launch_max;
-    if (!(cap > 0 && bytes > cap + cap / 2 && (int)p->plen.size() > b + n)) {
-        out.push_back({b, b + n});
-        return;
-    }
-    const int64_t *pre = p->plen.data();        // prefix sums of the piece lengths
-    for (int o = b; o < b + n;) {
-        // the first piece boundary at least cap bytes past o (lower_bound may return b + n + 1
-        // when fewer than cap bytes remain: clamp), then no runt dispatch at the end
-        int e = (int)(std::lower_bound(pre + o + 1, pre + b + n + 1, pre[o] + cap) - pre);
-        if (e > b + n) e = b + n;
-        if (b + n - e < 16 || pre[b + n] - pre[e] < cap / 2) e = b + n;
-        out.push_back({o, e});
-        o = e;
-    }
-}
+// Copy launches.  What a launch is -- its pieces, its kernel (copy_kernel_w<2 / 4 / 8> over
+// wave-sized pieces, copy_kernel_g<4> plain or non-temporal), its dispatches, its stream, the
+// mark behind it -- was decided when the plan was loaded (CopyLaunch, plan_load.hip); here the
+// table is walked.
 
-int launch_dispatches(const xg_plan *p, int b, int n, int64_t bytes)
-{
-    std::vector<std::pair<int, int>> cuts;
-    launch_cuts(p, b, n, bytes, cuts);
-    return (int)cuts.size();
-}
+// workgroups (4 waves each) of a copy_kernel_w dispatch over n pieces
+static int wave_wgs(const xg_plan *p, int n) { return std::max(1, std::min(p->ctx->wave_grid, (n + 3) / 4)); }
 
-static int launch_one(xg_plan *p, int b, int n, int v, hipStream_t st, unsigned long long *start)
+// One dispatch of launch l: pieces [b, b + n).  Only a launch's first dispatch runs
+// copy_kernel_w; the later ones of a cut wave launch copy their pieces with copy_kernel_g<4>.
+static int launch_one(xg_plan *p, const CopyLaunch &l, int b, int n, hipStream_t st, unsigned long long *start)
 {
     const xgk::DCopy *pc = p->d_pieces + b;
-    if (v == 1 && p->wave_at[b]) {       // pieces of <= wave_at[b] KiB, 16-B aligned (launch_chunk)
-        const int w = std::max(1, std::min(p->ctx->wave_grid, (n + 3) / 4));
-        if (p->wave_at[b] == 2)
-            hipLaunchKernelGGL((xgk::copy_kernel_w<2>), dim3(w), dim3(xgk::kThreads), 0, st, pc, n, start);
-        else if (p->wave_at[b] == 4)
-            hipLaunchKernelGGL((xgk::copy_kernel_w<4>), dim3(w), dim3(xgk::kThreads), 0, st, pc, n, start);
-        else
-            hipLaunchKernelGGL((xgk::copy_kernel_w<xgk::kWaveKiB>), dim3(w), dim3(xgk::kThreads), 0, st, pc, n, start);
-    } else if (v == 6) hipLaunchKernelGGL((xgk::copy_kernel_g<4, true>), dim3(n), dim3(xgk::kThreads), 0, st, pc, start);
-    else hipLaunchKernelGGL((xgk::copy_kernel_g<4>), dim3(n), dim3(xgk::kThreads), 0, st, pc, start);
+    if (l.kib && b == l.b) {
+        const auto k = l.kib == 2   ? xgk::copy_kernel_w<2>
+                       : l.kib == 4 ? xgk::copy_kernel_w<4>
+                                    : xgk::copy_kernel_w<xgk::kWaveKiB>;
+        hipLaunchKernelGGL(k, dim3(wave_wgs(p, n)), dim3(xgk::kThreads), 0, st, pc, n, start);
+    } else {
+        const auto k = l.nt ? xgk::copy_kernel_g<4, true> : xgk::copy_kernel_g<4>;
+        hipLaunchKernelGGL(k, dim3(n), dim3(xgk::kThreads), 0, st, pc, start);
+    }
     HIPCHK(hipGetLastError());
     return XG_OK;
 }
@@ -119,122 +89,70 @@ static int kt_after(xg_ctx *c, hipStream_t stream, bool kt, int64_t bytes)
     return XG_OK;
 }
 
-// One copy launch of pieces [b, b + n) moving `bytes`, as its dispatches (launch_cuts),
-// each bracketed by kernel-timing events when a per-launch session is on.  start: the
-// first dispatch stamps its start there (see copy_kernel_g).
-static int launch_copy(xg_plan *p, int b, int n, int64_t bytes, hipStream_t st, unsigned long long *start = nullptr,
-                       bool reread = false)
+// One copy launch as its dispatches, each bracketed by kernel-timing events when a per-launch
+// session is on.  start: the first dispatch stamps its start there (see copy_kernel_g).
+static int launch_copy(xg_plan *p, const CopyLaunch &l, hipStream_t st, unsigned long long *start)
 {
-    const int v = copy_variant(p, bytes, reread);
-    if (start && v != 1 && v != 6) return XG_EARG;
-    std::vector<std::pair<int, int>> cuts;
-    launch_cuts(p, b, n, bytes, cuts);
+    if (start && !l.stamps) return XG_EARG;
+    const int *cut = p->cuts.data() + l.cut;
     int rc;
-    for (const auto &q : cuts) {
-        const int64_t nb = cuts.size() == 1 ? bytes : p->plen[q.second] - p->plen[q.first];
+    for (int k = 0; k < l.ndisp; ++k) {
+        const int64_t nb = l.ndisp == 1 ? l.bytes : p->plen[cut[k + 1]] - p->plen[cut[k]];
         bool kt;
         if ((rc = kt_before(p->ctx, st, &kt))) return rc;
-        if ((rc = launch_one(p, q.first, q.second - q.first, v, st, q.first == b ? start : nullptr))) return rc;
+        if ((rc = launch_one(p, l, cut[k], cut[k + 1] - cut[k], st, k == 0 ? start : nullptr))) return rc;
         if ((rc = kt_after(p->ctx, st, kt, nb))) return rc;
     }
     return XG_OK;
 }
 
-// one copy launch, bracketed by kernel-timing events when a per-launch session is on
-static int timed_copy(xg_plan *p, int b, int n, int64_t bytes, hipStream_t stream, bool reread = false)
-{
-    return launch_copy(p, b, n, bytes, stream, nullptr, reread);
-}
-
-// step part 1: stage copies, then local gather/scatter + packs.  A split step
-// forks its local part onto `side`, where it runs beside the packs and the RCCL
-// group on `stream`; enqueue_post joins it back before the step ends.  A fused
-// step's first launch also holds the previous step's unpacks: the previous step
-// ends with it (its event, when recording, goes right behind it), and the local
-// part forks after it, so no message of this step lands before one of the previous.
-int enqueue_pre(xg_plan *p, int s, hipStream_t stream, hipStream_t side)
+// step part 1: the step's launches up to its RCCL group.  A side-stream launch (a split
+// step's local part) forks off `stream` and runs beside the packs and the RCCL group;
+// enqueue_post joins it back before the step ends.  A launch that holds the previous
+// step's unpacks ends that step: its mark, when marking, goes right behind it, and nothing
+// of this step comes before it, so no message of this step lands before one of the previous.
+// start: the step's first launch stamps its start there (chains).
+int enqueue_pre(xg_plan *p, int s, hipStream_t stream, hipStream_t side, unsigned long long *start)
 {
     const StepR &st = p->steps[s];
     int rc;
-    if (st.stage_n && (rc = timed_copy(p, st.stage_b, st.stage_n, st.stage_bytes, stream, true))) return rc;
-    if (st.fused) {
-        // the previous step's unpacks, [this step's local copies,] this step's packs: one launch
-        const StepR &pv = p->steps[s - 1];
-        const int n = pv.post_n + (st.fused_local ? st.local_n : 0) + st.pack_n;
-        const int64_t b = pv.post_bytes + (st.fused_local ? st.local_bytes : 0) + st.pack_bytes;
-        if ((rc = timed_copy(p, pv.post_b, n, b, stream, true))) return rc;
-        if (p->rec_ev && p->need_mark[s - 1] && (rc = mark(p, s - 1, stream))) return rc;
-    }
-    if (st.split) {
-        // the packs feed the RCCL group (the critical path), the local part does not: by default
-        // the local part forks after the pack launch, so it overlaps the transfer instead of
-        // sharing HBM with the packs (XG_SPLIT_AFTER_PACK=0: both at once, as in round 2)
-        const bool pack_here = !st.fused && st.pack_n;
-        if (pack_here && p->ctx->split_after_pack &&
-            (rc = timed_copy(p, st.pack_b, st.pack_n, st.pack_bytes, stream, true)))
-            return rc;
-        HIPCHK(hipEventRecord(p->fork[s], stream));
-        HIPCHK(hipStreamWaitEvent(side, p->fork[s], 0));
-        if ((rc = timed_copy(p, st.local_b, st.local_n, st.local_bytes, side))) return rc;
-        HIPCHK(hipEventRecord(p->join[s], side));
-        if (pack_here && !p->ctx->split_after_pack &&
-            (rc = timed_copy(p, st.pack_b, st.pack_n, st.pack_bytes, stream, true)))
-            return rc;
-    } else if (!st.fused && st.pre_n &&
-               (rc = timed_copy(p, st.local_b, st.pre_n, st.local_bytes + st.pack_bytes, stream,
-                                st.pack_n > 0 || st.stage_fused))) {
-        return rc;
+    for (int i = st.l_b; i < st.l_rccl; ++i) {
+        const CopyLaunch &l = p->launches[i];
+        if (l.side) {
+            HIPCHK(hipEventRecord(p->fork[s], stream));
+            HIPCHK(hipStreamWaitEvent(side, p->fork[s], 0));
+        }
+        if ((rc = launch_copy(p, l, l.side ? side : stream, i == st.l_b ? start : nullptr))) return rc;
+        if (l.side) HIPCHK(hipEventRecord(p->join[s], side));
+        if (l.mark_prev && p->rec_ev && p->need_mark[s - 1] && (rc = mark(p, s - 1, stream))) return rc;
     }
     return XG_OK;
 }
 
-// step part 3: unpack out of staging (unless deferred into the next step's fused
-// launch), then wait for the forked local part
+// step part 3: the launches behind the RCCL group (the unpacks, unless deferred into the
+// next step's launch), then wait for the forked local part
 int enqueue_post(xg_plan *p, int s, hipStream_t stream)
 {
     const StepR &st = p->steps[s];
     int rc;
-    if (st.post_n && !st.deferred && (rc = timed_copy(p, st.post_b, st.post_n, st.post_bytes, stream))) return rc;
-    if (st.split) HIPCHK(hipStreamWaitEvent(stream, p->join[s], 0));
+    for (int i = st.l_rccl; i < st.l_e; ++i)
+        if ((rc = launch_copy(p, p->launches[i], stream, nullptr))) return rc;
+    for (int i = st.l_b; i < st.l_rccl; ++i)
+        if (p->launches[i].side) HIPCHK(hipStreamWaitEvent(stream, p->join[s], 0));
     return XG_OK;
 }
 
-// The copy launches of one run that go to copy_kernel_w, counted dispatch by dispatch exactly as
-// enqueue_pre / enqueue_post issue them (launch_copy -> launch_cuts -> launch_one), and the
-// geometry launch_one gives them: w workgroups of 4 waves over n pieces.
+// The dispatches of one run that go to copy_kernel_w, and the geometry launch_one gives them:
+// w workgroups of 4 waves over n pieces.
 extern "C" int xg_plan_wave_launches(const xg_plan *p, int *grid, int *max_pieces_per_wave)
 {
     int count = 0, most = 0;
-    std::vector<std::pair<int, int>> cuts;
-    auto one = [&](int b, int n, int64_t bytes, bool reread) {
-        if (n <= 0) return;
-        const int v = copy_variant(p, bytes, reread);
-        launch_cuts(p, b, n, bytes, cuts);
-        for (const auto &q : cuts) {
-            if (!(v == 1 && p->wave_at[q.first])) continue;
-            const int m = q.second - q.first;
-            const int w = std::max(1, std::min(p->ctx->wave_grid, (m + 3) / 4));
-            ++count;
-            most = std::max(most, (m + 4 * w - 1) / (4 * w));
-        }
-    };
-    for (int s = 0; s < p->nsteps; ++s) {
-        if (p->seg_of[s] >= 0) continue;        // an engine segment's step: no copy launch
-        const StepR &st = p->steps[s];
-        one(st.stage_b, st.stage_n, st.stage_bytes, true);
-        if (st.fused) {
-            const StepR &pv = p->steps[s - 1];
-            one(pv.post_b, pv.post_n + (st.fused_local ? st.local_n : 0) + st.pack_n,
-                pv.post_bytes + (st.fused_local ? st.local_bytes : 0) + st.pack_bytes, true);
-        }
-        if (st.split) {
-            if (!st.fused) one(st.pack_b, st.pack_n, st.pack_bytes, true);
-            one(st.local_b, st.local_n, st.local_bytes, false);
-        } else if (!st.fused) {
-            one(st.local_b, st.pre_n, st.local_bytes + st.pack_bytes, st.pack_n > 0 || st.stage_fused);
-        }
-        if (!st.deferred) one(st.post_b, st.post_n, st.post_bytes, false);
-    }
+    each_launch(p, [&](const CopyLaunch &l) {
+        if (!l.kib) return;
+        const int m = p->cuts[l.cut + 1] - l.b, w = wave_wgs(p, m);
+        ++count;
+        most = std::max(most, (m + 4 * w - 1) / (4 * w));
+    });
     if (grid) *grid = p->ctx->wave_grid;
     if (max_pieces_per_wave) *max_pieces_per_wave = most;
     return count;
@@ -297,31 +215,22 @@ int launch_seg(xg_plan *p, const EngSeg &g, hipStream_t stream, bool armed)
     if ((rc = kt_before(c, stream, &kt))) return rc;
     unsigned long long *stamps = reinterpret_cast<unsigned long long *>(p->d_engine + 1) + g.s0;
     const int *sb = p->d_sb + g.sb_off;
-    if (g.solo && g.wv == 1 && g.gran == 16)
-        hipLaunchKernelGGL((xgk::solo_engine_kernel<xgk::kSoloK, 1>), dim3(g.w), dim3(64), 0, stream,
-                           p->d_solo + g.u0, g.npieces, g.sbase, g.dbase, sb, n, p->d_engine, stamps, p->nsteps,
-                           db, epoch);
-    else if (g.solo && g.wv == 1 && g.gran == 4)
-        hipLaunchKernelGGL((xgk::solo_engine_kernel<xgk::kSoloK, 1, 4>), dim3(g.w), dim3(64), 0, stream,
-                           p->d_solo + g.u0, g.npieces, g.sbase, g.dbase, sb, n, p->d_engine, stamps, p->nsteps,
-                           db, epoch);
-    else if (g.solo && g.wv == 1)      // granule 1: 16 registers per piece and lane, half the rows per chunk
-        hipLaunchKernelGGL((xgk::solo_engine_kernel<xgk::kSoloK / 2, 1, 1>), dim3(g.w), dim3(64), 0, stream,
-                           p->d_solo + g.u0, g.npieces, g.sbase, g.dbase, sb, n, p->d_engine, stamps, p->nsteps,
-                           db, epoch);
-    else if (g.solo)
-        hipLaunchKernelGGL((xgk::solo_engine_kernel<xgk::kSoloK, xgk::kSoloWaves>), dim3(g.w), dim3(xgk::kSoloThreads), 0,
-                           stream, p->d_solo + g.u0, g.npieces, g.sbase, g.dbase, sb, n, p->d_engine, stamps, p->nsteps,
-                           db, epoch);
-    else if (g.b == 1)
-        hipLaunchKernelGGL(xgk::step_engine_kernel<1>, dim3(g.w), dim3(xgk::kThreads), 0, stream, p->d_epieces, sb, n,
-                           p->d_engine, stamps, base, db, epoch);
-    else if (g.b == 4)
-        hipLaunchKernelGGL(xgk::step_engine_kernel<4>, dim3(g.w), dim3(xgk::kThreads), 0, stream, p->d_epieces, sb, n,
-                           p->d_engine, stamps, base, db, epoch);
-    else
-        hipLaunchKernelGGL(xgk::step_engine_kernel<16>, dim3(g.w), dim3(xgk::kThreads), 0, stream, p->d_epieces, sb,
-                           n, p->d_engine, stamps, base, db, epoch);
+    if (g.solo) {
+        // one-wave rails by granule (granule 1: 16 registers per piece and lane, half the rows
+        // per chunk), or workgroup rails
+        const auto k = g.wv != 1     ? xgk::solo_engine_kernel<xgk::kSoloK, xgk::kSoloWaves>
+                       : g.gran == 16 ? xgk::solo_engine_kernel<xgk::kSoloK, 1>
+                       : g.gran == 4  ? xgk::solo_engine_kernel<xgk::kSoloK, 1, 4>
+                                      : xgk::solo_engine_kernel<xgk::kSoloK / 2, 1, 1>;
+        hipLaunchKernelGGL(k, dim3(g.w), dim3(g.wv != 1 ? xgk::kSoloThreads : 64), 0, stream, p->d_solo + g.u0,
+                           g.npieces, g.sbase, g.dbase, sb, n, p->d_engine, stamps, p->nsteps, db, epoch);
+    } else {
+        const auto k = g.b == 1   ? xgk::step_engine_kernel<1>
+                       : g.b == 4 ? xgk::step_engine_kernel<4>
+                                  : xgk::step_engine_kernel<16>;
+        hipLaunchKernelGGL(k, dim3(g.w), dim3(xgk::kThreads), 0, stream, p->d_epieces, sb, n, p->d_engine, stamps,
+                           base, db, epoch);
+    }
     HIPCHK(hipGetLastError());
     return kt_after(c, stream, kt, g.bytes);
 }
@@ -437,17 +346,8 @@ static int enqueue_run(xg_plan *p, double *step_post)
             const int ce = p->chain_end[s];
             for (int t = s; t < ce; ++t) {
                 const double tq = xg_now();
-                const StepR &st = p->steps[t];
                 // the step's first launch stamps the previous step's completion
-                unsigned long long *start = t > s ? p->d_cstamp + t - 1 : nullptr;
-                rc = XG_OK;
-                if (st.stage_n) {
-                    rc = launch_copy(p, st.stage_b, st.stage_n, st.stage_bytes, c->stream, start, true);
-                    start = nullptr;
-                }
-                if (!rc && st.local_n)
-                    rc = launch_copy(p, st.local_b, st.local_n, st.local_bytes, c->stream, start, st.stage_fused);
-                if (rc) {
+                if ((rc = enqueue_pre(p, t, c->stream, c->side, t > s ? p->d_cstamp + t - 1 : nullptr))) {
                     p->rec_ev = false;
                     return rc;
                 }

@@ -1,5 +1,6 @@
-// plan_load.hip -- xg_plan_load: a device plan (libxghost) becomes the piece table, each step's
-// launch form, the engine segments and the staging displacements (device scan).
+// plan_load.hip -- xg_plan_load: a device plan (libxghost) becomes the piece table, the table of
+// copy launches (each step's launches, decided here once: build_tables), the engine segments
+// and the staging displacements (device scan).
 #include "rt.h"
 
 static uint64_t next_plan_id()
@@ -380,102 +381,184 @@ static int run_displ_scan(xg_plan *p, DisplScan &ds)
 }
 
 
-// Device half of a plan load: the piece table, the step events, the displacement scan
-// and the engine segments.  On an error the caller frees the plan (xg_plan_free takes a
-// half-loaded one: every handle starts null).
-static int plan_upload(xg_plan *p, const std::vector<xgk::DCopy> &pieces, DisplScan &ds)
+// Pass 1 of a load: per step, what it holds, its RCCL calls and its form (split, fused,
+// fused_local, stage_fused, deferred, self_local).  false: a descriptor outside its region.
+static bool step_forms(xg_plan *p, const xg_devplan *dp)
 {
-    int rc;
-    if (p->npieces) {
-        HIPCHK(hipMalloc(&p->d_pieces, sizeof(xgk::DCopy) * pieces.size()));
-        HIPCHK(hipMemcpy(p->d_pieces, pieces.data(), sizeof(xgk::DCopy) * pieces.size(), hipMemcpyHostToDevice));
-    }
-    p->need_mark.assign(p->nsteps, 1);
-    p->fork.assign(p->nsteps, nullptr);
-    p->join.assign(p->nsteps, nullptr);
-    for (int s = 0; s < p->nsteps; ++s)
-        if (p->steps[s].split) {
-            HIPCHK(hipEventCreateWithFlags(&p->fork[s], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&p->join[s], hipEventDisableTiming));
+    const xg_ctx *c = p->ctx;
+    const xg_regions *r = p->reg;
+    p->steps.resize(dp->nsteps);
+    for (int s = 0; s < dp->nsteps; ++s) {
+        const xg_stepplan &sp = dp->steps[s];
+        StepR &st = p->steps[s];
+        if (sp.stage_count < 0 || sp.stage_count > sp.pre_count || sp.post_count < 0) return false;
+        int nloc = 0, npack = 0;
+        for (int i = sp.stage_count; i < sp.pre_count; ++i) {
+            const bool pack = dp->copies[sp.pre_begin + i].dst_buf == XG_BUF_STAGE_SEND;
+            if (!pack && npack) return false;                   // the plan lists local copies, then packs
+            (pack ? npack : nloc) += dp->copies[sp.pre_begin + i].len > 0;
         }
-    HIPCHK(hipMalloc(&p->d_gstamp, 8 * ((size_t)p->nsteps + 1)));
-    if ((rc = run_displ_scan(p, ds)) || (rc = build_segments(p, pieces))) return rc;
-    return XG_OK;
+        for (int i = 0; i < sp.post_count; ++i)
+            if (dp->copies[sp.post_begin + i].src_buf != XG_BUF_STAGE_RECV) return false;   // post copies unpack
+        // the step's RCCL calls: exactly what libxghost says this GPU posts (calls.c)
+        const int nc = xg_devplan_step_calls(dp, s, c->self_max, nullptr);
+        if (nc < 0) return false;
+        st.self_local = xg_devplan_step_self_calls(dp, s, c->self_max) > 0;
+        st.call_b = (int)p->calls.size();
+        st.call_n = nc;
+        p->call_begin.push_back(st.call_b);
+        p->calls.resize(st.call_b + nc);
+        xg_devplan_step_calls(dp, s, c->self_max, p->calls.data() + st.call_b);
+        st.posts = sp.posts;
+        for (int i = 0; i < nc; ++i) {
+            const xg_call &o = p->calls[st.call_b + i];
+            if (o.kind == XG_CALL_BARRIER) {
+                st.sync_after = c->nranks > 1;
+                continue;
+            }
+            if (o.kind == XG_CALL_FENCE) {        // a relay step's second RCCL group follows
+                st.groups++;
+                continue;
+            }
+            if ((o.kind != XG_CALL_SEND && o.kind != XG_CALL_RECV) || o.peer < 0 || o.peer >= c->nranks ||
+                (o.peer == c->rank && !st.self_local) || o.buf < 0 || o.buf >= XG_NBUF || o.off < 0 ||
+                o.len < 0 || o.off + o.len > r->bytes[o.buf])
+                return false;
+            st.p2p_n++;
+        }
+        if (st.self_local) nloc = 0;        // the local copies travel in the step's RCCL group
+        int64_t b_loc = 0;
+        for (int i = sp.stage_count; i < sp.pre_count; ++i)
+            if (dp->copies[sp.pre_begin + i].dst_buf != XG_BUF_STAGE_SEND && !st.self_local)
+                b_loc += std::max<int64_t>(0, dp->copies[sp.pre_begin + i].len);
+        // a cross-GPU step's local part runs on the side stream beside the packs and the RCCL
+        // group (split) when it is large enough to pay for the fork / join; a smaller one joins
+        // the step's first launch -- the fused one too, if it touches none of the bytes the
+        // previous step's unpacks write (then the step is ONE copy launch + its RCCL group)
+        st.split = st.p2p_n > 0 && nloc > 0 && b_loc >= c->split_min;
+        const bool prev_ok = s > 0 && npack > 0 && sp.stage_count == 0 &&
+                             !p->steps[s - 1].sync_after && dp->steps[s - 1].post_count > 0;
+        st.fused = prev_ok && (st.split || nloc == 0 || !xg_step_local_meets_unpacks(dp, s));
+        st.fused_local = st.fused && !st.split && nloc > 0;
+        // TAM: a step's stage copies share the local (+ pack) launch when none of those meets
+        // their bytes -- README m15 / m16 step 3: 6 -> 5 launches per run
+        st.stage_fused = c->fuse_stage && sp.stage_count > 0 && (nloc > 0 || npack > 0) && !st.split &&
+                         !st.fused && !st.self_local && xg_step_stage_meets_rest(dp, s) == 0;
+        if (st.fused) p->steps[s - 1].deferred = true;
+    }
+    p->call_begin.push_back((int32_t)p->calls.size());
+    return true;
 }
 
-extern "C" int xg_plan_load(xg_ctx *c, xg_regions *r, const xg_devplan *dp, xg_plan **out)
+// Whether one run copies more than the Infinity Cache holds: decides each launch's variant
+// (copy_variant).
+static bool plan_streams(const xg_plan *p, const xg_devplan *dp)
 {
-    if (!c || !r || !dp || !out) return XG_EARG;
-    if (dp->ngpus != c->nranks || dp->gpu != c->rank) {
-        fprintf(stderr, "xg_plan_load: plan for gpu %d/%d loaded on rank %d/%d\n", dp->gpu, dp->ngpus, c->rank,
-                c->nranks);
-        return XG_EARG;
-    }
-    for (int i = 0; i < XG_NBUF; ++i)
-        if (dp->region_bytes[i] > r->bytes[i]) {
-            fprintf(stderr, "xg_plan_load: region %d too small (%lld < %lld)\n", i, (long long)r->bytes[i],
-                    (long long)dp->region_bytes[i]);
-            return XG_EARG;
+    // the bytes one run copies (as the StepR totals add them up)
+    int64_t run = 0;
+    for (int s = 0; s < dp->nsteps; ++s) {
+        const xg_stepplan &sp = dp->steps[s];
+        for (int i = 0; i < sp.pre_count; ++i) {
+            const xg_copy &cp = dp->copies[sp.pre_begin + i];
+            const bool local = i >= sp.stage_count && cp.dst_buf != XG_BUF_STAGE_SEND;
+            if (!(local && p->steps[s].self_local)) run += std::max<int64_t>(0, cp.len);
         }
-    HIPCHK(hipSetDevice(c->device));
-    xg_plan *p = new xg_plan();
-    p->ctx = c; p->reg = r; p->nsteps = dp->nsteps; p->variant = c->variant; p->streaming = false;
-    p->d_pieces = nullptr; p->d_sb = nullptr; p->d_epieces = nullptr; p->d_engine = nullptr; p->d_disp = nullptr;
-    p->ndisp = 0; p->engine_base = 0; p->engine_reset = false; p->nlaunch = 0;
-    p->db = nullptr; p->epoch = 0; p->d_solo = nullptr; p->rec_ev = false; p->stamp_rails = 1; p->d_cstamp = nullptr;
-    p->g_enq = p->g_run = nullptr; p->id = next_plan_id(); p->vg.rccl = false; p->vg.exec = nullptr;
-    p->d_gstamp = nullptr; p->graph_auto = false; p->local_only = false;
-    // One piece per workgroup.  Bytes per piece, per launch (launch_chunk over the launch's
-    // copies): c->chunk (32 KiB: profiles/r01_copy_ab.txt) or c->chunk / 2, / 4, / 8 (>= 4 KiB;
-    // a halving keeps dividing the power-of-two segment sizes: no ragged tail piece per segment,
-    // profiles/r01_min_pieces_ab.txt), whichever gives the least work to the busiest CU: a
-    // launch of w pieces of c bytes puts ceil(w / CUs) pieces on some CU, each costing c bytes
-    // plus a fixed per-workgroup start (kWgCost = 2 KiB bytes-equivalent); ties
-    // keep the larger piece.  A 28 MiB pack of 256 KiB segments: 896 pieces of 32 KiB = 3.5
-    // per CU (the busiest 4 x 32 KiB) -> 1792 of 16 KiB = exactly 7 (7 x 16 KiB).  The bench's
-    // 448 MiB launches stay 32 KiB (56 per CU).  (A rule
-    // forcing >= 2 x CUs pieces on small launches was measured 3-7 % slower and dropped:
+        for (int i = 0; i < sp.post_count; ++i) run += std::max<int64_t>(0, dp->copies[sp.post_begin + i].len);
+    }
+    // ... and whether its regions could hold in it at all: -k repetitions re-copy the same
+    // bytes, so a run of many small repetitions (P32 A14 -d 64 KiB -k 50: 56 MiB of
+    // regions, 2.8 GB copied) stays cache-resident and copies with plain stores
+    int64_t foot = 0;
+    for (int i = 0; i < XG_NBUF; ++i) foot += std::max<int64_t>(0, dp->region_bytes[i]);
+    return std::min(2 * run, foot) > ((int64_t)256 << 20);
+}
+
+// The copy kernel variant of a launch moving `bytes`.  Variant 0 picks non-temporal
+// loads/stores (6) when the bytes cannot come back from the 256 MiB Infinity Cache: a
+// launch whose own source + destination exceed it, or a launch of >= kNtStream bytes in a
+// plan whose run copies more than it (every step then finds its bytes evicted by the steps
+// before) -- unless what it writes is read again at once (`reread`: packs feeding RCCL, TAM
+// stage copies), which then may still find it in the cache; plain (1) otherwise.
+static int copy_variant(const xg_plan *p, int64_t bytes, bool reread)
+{
+    if (p->variant) return p->variant;
+    return bytes >= kNtMin || (!reread && p->streaming && bytes >= kNtStream) ? 6 : 1;
+}
+
+// Pass 2 of a load: the piece table and the launch table together, launch by launch -- a
+// launch's pieces are contiguous and cut for that launch's bytes, and its table entry (kernel
+// form, stream, mark) is decided where its pieces are cut.  Host work only.
+struct TableBuilder {
+    typedef std::pair<int, int> Range;      // copies [first, first + second) of dp->copies
+    xg_plan *p;
+    const xg_devplan *dp;
+    std::vector<xgk::DCopy> &pieces;
+    DisplScan &ds;
+    int64_t chunk = 0;                      // bytes per piece of the open launch
+    CopyLaunch *cur = nullptr;              // the open launch
+
+    int64_t bytes_of(Range rg) const
+    {
+        int64_t n = 0;
+        for (int i = 0; i < rg.second; ++i) n += std::max<int64_t>(0, dp->copies[rg.first + i].len);
+        return n;
+    }
+
+    // Open launch `l` over the copies of `ranges`: its first piece, bytes, kernel form and the
+    // size its pieces are cut to.
+    // One piece per workgroup.  Bytes per piece: c->chunk (32 KiB: profiles/r01_copy_ab.txt) or
+    // c->chunk / 2, / 4, / 8 (>= 4 KiB; a halving keeps dividing the power-of-two segment sizes:
+    // no ragged tail piece per segment, profiles/r01_min_pieces_ab.txt), whichever gives the least
+    // work to the busiest CU: a launch of w pieces of c bytes puts ceil(w / CUs) pieces on some
+    // CU, each costing c bytes plus a fixed per-workgroup start (kWgCost = 2 KiB
+    // bytes-equivalent); ties keep the larger piece.  A 28 MiB pack of 256 KiB segments: 896
+    // pieces of 32 KiB = 3.5 per CU (the busiest 4 x 32 KiB) -> 1792 of 16 KiB = exactly 7
+    // (7 x 16 KiB).  The bench's 448 MiB launches stay 32 KiB (56 per CU).  (A rule forcing
+    // >= 2 x CUs pieces on small launches was measured 3-7 % slower and dropped:
     // profiles/r03/min_wg/summary.txt.)
-    // A launch of a cross-GPU step (packs, unpacks, its local part), or of a GPU-local step too
-    // large for the step engine, that copies with plain loads and stores, every transfer 16-B
-    // aligned, of >= wave_min bytes: copy_kernel_w over pieces of kWaveKiB (wave_at marks its
-    // first piece with the launch's piece KiB, wave_kib_for; profiles/r03/wave_copy/).
-    int64_t chunk = c->chunk;
-    std::vector<xgk::DCopy> pieces;
-    std::vector<char> wave_at;
-    auto launch_chunk = [&](std::initializer_list<std::pair<int, int>> ranges, bool cross = false,
-                            bool reread = false) {
+    // `cross`: a launch of a cross-GPU step (packs, unpacks, its local part), or of a GPU-local
+    // step too large for the step engine.  One that copies with plain loads and stores, every
+    // transfer 16-B aligned, of wave_min .. kWaveMax bytes, is cut into pieces of 8 / 4 / 2 KiB
+    // (wave_kib_for; profiles/r03/wave_copy/) and runs copy_kernel_w.
+    // `reread` (copy_variant) comes twice: for the cut of the pieces and for the kernel.  They
+    // differ in one launch only (step(), the local + pack launch); where the cut says plain and
+    // the kernel non-temporal, the wave-sized pieces run copy_kernel_g<4, true>.
+    void open(CopyLaunch &l, std::initializer_list<Range> ranges, bool cross, bool reread_cut, bool reread_run)
+    {
+        const xg_ctx *c = p->ctx;
+        cur = &l;
+        l.b = (int)pieces.size();
         chunk = c->chunk;
-        const size_t first = pieces.size();
-        if (wave_at.size() <= first) wave_at.resize(first + 1, 0);
-        wave_at[first] = 0;
-        int64_t bytes = 0;
         uint64_t bits = 0;
-        for (const auto &rg : ranges)
+        std::vector<int64_t> lens;
+        for (const Range &rg : ranges)
             for (int i = 0; i < rg.second; ++i) {
                 const xg_copy &cp = dp->copies[rg.first + i];
+                lens.push_back(cp.len);
                 if (cp.len <= 0) continue;
-                bytes += cp.len;
+                l.bytes += cp.len;
                 bits |= (uint64_t)cp.src_off | (uint64_t)cp.dst_off | (uint64_t)cp.len;
             }
-        if (bytes <= 0) return;
-        if (cross && bytes >= c->wave_min && bytes <= kWaveMax && (bits & 15) == 0 &&
-            copy_variant(p, bytes, reread) == 1) {
-            const int kib = c->wave_kib ? c->wave_kib : wave_kib_for(bytes, c->cus);
+        if (l.bytes <= 0) return;
+        const int v = copy_variant(p, l.bytes, reread_run);
+        l.nt = v == 6;
+        l.stamps = v == 1 || v == 6;
+        if (cross && l.bytes >= c->wave_min && l.bytes <= kWaveMax && (bits & 15) == 0 &&
+            copy_variant(p, l.bytes, reread_cut) == 1) {
+            const int kib = c->wave_kib ? c->wave_kib : wave_kib_for(l.bytes, c->cus);
             chunk = (int64_t)kib << 10;
-            wave_at[first] = (char)kib;
-            return;
+            if (v == 1) l.kib = kib;
+        } else {
+            chunk = xg_piece_size(lens.data(), (int)lens.size(), c->chunk, c->cus, kWgCost);
         }
-        std::vector<int64_t> lens;
-        for (const auto &rg : ranges)
-            for (int i = 0; i < rg.second; ++i) lens.push_back(dp->copies[rg.first + i].len);
-        chunk = xg_piece_size(lens.data(), (int)lens.size(), c->chunk, c->cus, kWgCost);
-    };
-    DisplScan ds;
-    int rc;
+    }
+    void close() { cur->n = (int)pieces.size() - cur->b; }
+
     // side: -1 plain copy; 0 pack (destination in STAGE_SEND, displacement from the
     // device scan); 1 unpack (source in STAGE_RECV, likewise)
-    auto add = [&](const xg_copy &cp, int side) -> bool {
+    bool add(const xg_copy &cp, int side)
+    {
+        const xg_regions *r = p->reg;
         if (cp.len <= 0) return true;
         if (cp.src_buf < 0 || cp.src_buf >= XG_NBUF || cp.dst_buf < 0 || cp.dst_buf >= XG_NBUF) return false;
         if (cp.src_off < 0 || cp.dst_off < 0 || cp.src_off + cp.len > r->bytes[cp.src_buf] ||
@@ -496,288 +579,292 @@ extern "C" int xg_plan_load(xg_ctx *c, xg_regions *r, const xg_devplan *dp, xg_p
             pieces.push_back(d);
         }
         return true;
-    };
-    p->steps.resize(dp->nsteps);
-    // pass 1: per step, what it holds and how it launches
-    for (int s = 0; s < dp->nsteps; ++s) {
-        const xg_stepplan &sp = dp->steps[s];
-        StepR &st = p->steps[s];
-        if (sp.stage_count < 0 || sp.stage_count > sp.pre_count || sp.post_count < 0) goto bad;
-        int nloc = 0, npack = 0;
-        for (int i = sp.stage_count; i < sp.pre_count; ++i) {
-            const bool pack = dp->copies[sp.pre_begin + i].dst_buf == XG_BUF_STAGE_SEND;
-            if (!pack && npack) goto bad;                       // the plan lists local copies, then packs
-            (pack ? npack : nloc) += dp->copies[sp.pre_begin + i].len > 0;
-        }
-        for (int i = 0; i < sp.post_count; ++i)
-            if (dp->copies[sp.post_begin + i].src_buf != XG_BUF_STAGE_RECV) goto bad;   // post copies unpack
-        {
-            // the step's RCCL calls: exactly what libxghost says this GPU posts (calls.c)
-            const int nc = xg_devplan_step_calls(dp, s, c->self_max, nullptr);
-            if (nc < 0) goto bad;
-            st.self_local = xg_devplan_step_self_calls(dp, s, c->self_max) > 0;
-            st.call_b = (int)p->calls.size();
-            st.call_n = nc;
-            p->call_begin.push_back(st.call_b);
-            p->calls.resize(st.call_b + nc);
-            xg_devplan_step_calls(dp, s, c->self_max, p->calls.data() + st.call_b);
-            st.p2p_n = 0;
-            st.sync_after = 0;
-            st.groups = 1;
-            st.posts = sp.posts;
-            for (int i = 0; i < nc; ++i) {
-                const xg_call &o = p->calls[st.call_b + i];
-                if (o.kind == XG_CALL_BARRIER) {
-                    st.sync_after = c->nranks > 1;
-                    continue;
-                }
-                if (o.kind == XG_CALL_FENCE) {        // a relay step's second RCCL group follows
-                    st.groups++;
-                    continue;
-                }
-                if ((o.kind != XG_CALL_SEND && o.kind != XG_CALL_RECV) || o.peer < 0 || o.peer >= c->nranks ||
-                    (o.peer == c->rank && !st.self_local) || o.buf < 0 || o.buf >= XG_NBUF || o.off < 0 ||
-                    o.len < 0 || o.off + o.len > r->bytes[o.buf])
-                    goto bad;
-                st.p2p_n++;
-            }
-        }
-        if (st.self_local) nloc = 0;        // the local copies travel in the step's RCCL group
-        int64_t b_loc = 0;
-        for (int i = sp.stage_count; i < sp.pre_count; ++i)
-            if (dp->copies[sp.pre_begin + i].dst_buf != XG_BUF_STAGE_SEND && !st.self_local)
-                b_loc += std::max<int64_t>(0, dp->copies[sp.pre_begin + i].len);
-        // a cross-GPU step's local part runs on the side stream beside the packs and the RCCL
-        // group (split) when it is large enough to pay for the fork / join; a smaller one joins
-        // the step's first launch -- the fused one too, if it touches none of the bytes the
-        // previous step's unpacks write (then the step is ONE copy launch + its RCCL group)
-        st.split = st.p2p_n > 0 && nloc > 0 && b_loc >= c->split_min;
-        st.deferred = false;
-        const bool prev_ok = s > 0 && npack > 0 && sp.stage_count == 0 &&
-                             !p->steps[s - 1].sync_after && dp->steps[s - 1].post_count > 0;
-        st.fused = prev_ok && (st.split || nloc == 0 || !xg_step_local_meets_unpacks(dp, s));
-        st.fused_local = st.fused && !st.split && nloc > 0;
-        // TAM: a step's stage copies share the local (+ pack) launch when none of those meets
-        // their bytes -- README m15 / m16 step 3: 6 -> 5 launches per run
-        st.stage_fused = c->fuse_stage && sp.stage_count > 0 && (nloc > 0 || npack > 0) && !st.split &&
-                         !st.fused && !st.self_local && xg_step_stage_meets_rest(dp, s) == 0;
-        if (st.fused) p->steps[s - 1].deferred = true;
     }
-    p->call_begin.push_back((int32_t)p->calls.size());
+    bool add_range(Range rg, int side)
     {
-        // the bytes one run copies (as the StepR totals below add them up): whether the plan
-        // streams past the Infinity Cache decides each launch's variant (copy_variant)
-        int64_t run = 0;
-        for (int s = 0; s < dp->nsteps; ++s) {
-            const xg_stepplan &sp = dp->steps[s];
-            for (int i = 0; i < sp.pre_count; ++i) {
-                const xg_copy &cp = dp->copies[sp.pre_begin + i];
-                const bool local = i >= sp.stage_count && cp.dst_buf != XG_BUF_STAGE_SEND;
-                if (!(local && p->steps[s].self_local)) run += std::max<int64_t>(0, cp.len);
-            }
-            for (int i = 0; i < sp.post_count; ++i) run += std::max<int64_t>(0, dp->copies[sp.post_begin + i].len);
-        }
-        // ... and whether its regions could hold in it at all: -k repetitions re-copy the same
-        // bytes, so a run of many small repetitions (P32 A14 -d 64 KiB -k 50: 56 MiB of
-        // regions, 2.8 GB copied) stays cache-resident and copies with plain stores
-        int64_t foot = 0;
-        for (int i = 0; i < XG_NBUF; ++i) foot += std::max<int64_t>(0, dp->region_bytes[i]);
-        p->streaming = std::min(2 * run, foot) > ((int64_t)256 << 20);
+        for (int i = 0; i < rg.second; ++i)
+            if (!add(dp->copies[rg.first + i], side)) return false;
+        return true;
     }
-    // pass 2: the piece table, each launch's pieces contiguous (a fused launch: the
-    // previous step's unpacks, then this step's packs)
-    for (int s = 0; s < dp->nsteps; ++s) {
+    int64_t span(int b) const
+    {
+        int64_t n = 0;
+        for (int i = b; i < (int)pieces.size(); ++i) n += pieces[i].len;
+        return n;
+    }
+    // step t's unpacks, into the open launch (t's own, or the fused launch of step t + 1)
+    bool add_post(int t)
+    {
+        const xg_stepplan &tp = dp->steps[t];
+        StepR &tt = p->steps[t];
+        tt.post_b = (int)pieces.size();
+        if (!add_range({tp.post_begin, tp.post_count}, 1)) return false;
+        ds.close_group();
+        tt.post_n = (int)pieces.size() - tt.post_b;
+        tt.post_bytes = span(tt.post_b);
+        return true;
+    }
+
+    // One step: at most four launches -- stage | local | packs | unpacks, in piece order.
+    //   stage_fused: stage, local and packs are ONE launch (`local`; the stage pieces count as
+    //   local ones); fused_local: the previous step's unpacks, local and packs are ONE launch
+    //   (`local`); split: `local` alone on the side stream, `pack` (fused: with the previous
+    //   unpacks in front) on the main one; fused with no local copies: `pack` alone; else local
+    //   and packs are ONE launch (`local`).
+    bool step(int s)
+    {
+        const xg_ctx *c = p->ctx;
         const xg_stepplan &sp = dp->steps[s];
         StepR &st = p->steps[s];
-        auto span = [&](int b) {
-            int64_t n = 0;
-            for (int i = b; i < (int)pieces.size(); ++i) n += pieces[i].len;
-            return n;
-        };
-        auto add_post = [&](int t) -> bool {      // (chunk set by the caller for its launch)
-            const xg_stepplan &tp = dp->steps[t];
-            StepR &tt = p->steps[t];
-            tt.post_b = (int)pieces.size();
-            for (int i = 0; i < tp.post_count; ++i)
-                if (!add(dp->copies[tp.post_begin + i], 1)) return false;
-            ds.close_group();
-            tt.post_n = (int)pieces.size() - tt.post_b;
-            tt.post_bytes = span(tt.post_b);
-            return true;
-        };
-        // each launch's pieces cut for that launch's bytes (launch_chunk): stage | local (+ packs,
-        // unless split) | [previous unpacks +] packs | unpacks
         int first_pack = sp.pre_count;
         for (int i = sp.stage_count; i < sp.pre_count; ++i)
             if (dp->copies[sp.pre_begin + i].dst_buf == XG_BUF_STAGE_SEND) {
                 first_pack = i;
                 break;
             }
-        const std::pair<int, int> r_stage{sp.pre_begin, sp.stage_count},
+        const Range r_stage{sp.pre_begin, sp.stage_count},
             r_local{sp.pre_begin + sp.stage_count, st.self_local ? 0 : first_pack - sp.stage_count},
             r_pack{sp.pre_begin + first_pack, sp.pre_count - first_pack},
             r_prev{st.fused ? dp->steps[s - 1].post_begin : 0, st.fused ? dp->steps[s - 1].post_count : 0},
             r_post{sp.post_begin, sp.post_count};
-        int64_t b_local = 0;
-        for (int i = 0; i < r_local.second; ++i) b_local += std::max<int64_t>(0, dp->copies[r_local.first + i].len);
+        // a GPU-local step's launch counts as cross too when it cannot be an engine step (larger
+        // than engine_max_step, or the engine off): one large one-off launch
+        const bool cross = st.p2p_n > 0 || r_pack.second > 0 || c->engine_max_step <= 0 ||
+                           bytes_of(r_local) > c->engine_max_step;
+        CopyLaunch stage, local, pack, post;        // n stays 0: the step has no such launch
+        st.stage_b = (int)pieces.size();
         if (st.stage_fused) {
-            // stage | local | packs as ONE launch (the stage pieces count as local ones)
-            launch_chunk({r_stage, r_local, r_pack}, st.p2p_n > 0 || r_pack.second > 0 || c->engine_max_step <= 0 ||
-                                                         b_local > c->engine_max_step, true);
-            st.stage_b = (int)pieces.size();
-            for (int i = 0; i < sp.stage_count; ++i)
-                if (!add(dp->copies[sp.pre_begin + i], -1)) goto bad;
-            st.stage_n = 0;
-            st.stage_bytes = 0;
+            open(local, {r_stage, r_local, r_pack}, cross, true, true);
+            if (!add_range(r_stage, -1)) return false;
         } else {
-            launch_chunk({r_stage});
-            st.stage_b = (int)pieces.size();
-            for (int i = 0; i < sp.stage_count; ++i)
-                if (!add(dp->copies[sp.pre_begin + i], -1)) goto bad;
-            st.stage_n = (int)pieces.size() - st.stage_b;
-            st.stage_bytes = span(st.stage_b);
-        }
-        // piece order: stage | local | [previous unpacks] | packs (split or not fused), or
-        // stage | previous unpacks | local | packs (fused_local: one launch over all three)
-        if (st.fused_local) {
-            launch_chunk({r_prev, r_local, r_pack}, true, true);
-            if (!add_post(s - 1)) goto bad;
-        } else if (!st.stage_fused) {
-            // a GPU-local step's launch too, when it cannot be an engine step (larger than
-            // engine_max_step, or the engine off): one large one-off launch
-            const bool big_local = c->engine_max_step <= 0 || b_local > c->engine_max_step;
-            if (st.split) launch_chunk({r_local}, true);
-            else launch_chunk({r_local, r_pack}, st.p2p_n > 0 || r_pack.second > 0 || big_local, r_pack.second > 0);
+            open(stage, {r_stage}, false, true, true);      // read again at once by the step's own copies
+            if (!add_range(r_stage, -1)) return false;
+            close();
+            st.stage_n = stage.n;
+            st.stage_bytes = stage.bytes;
+            if (st.fused_local) {
+                open(local, {r_prev, r_local, r_pack}, true, true, true);
+                local.mark_prev = true;
+                if (!add_post(s - 1)) return false;
+            } else if (st.split) {
+                open(local, {r_local}, true, false, false);
+                local.side = true;
+            } else if (!st.fused) {
+                // the cut asks whether the step lists packs, the kernel whether any holds bytes:
+                // they part for a step whose packs are all empty
+                open(local, {r_local, r_pack}, cross, r_pack.second > 0, bytes_of(r_pack) > 0);
+            }
         }
         st.local_b = st.stage_fused ? st.stage_b : (int)pieces.size();
-        for (int i = sp.stage_count; i < first_pack && !st.self_local; ++i)
-            if (!add(dp->copies[sp.pre_begin + i], -1)) goto bad;
+        if (!add_range(r_local, -1)) return false;
         st.local_n = (int)pieces.size() - st.local_b;
         st.local_bytes = span(st.local_b);
-        if (!st.fused_local) {
-            if (st.split || st.fused) launch_chunk({r_prev, r_pack}, true, true);
-            if (st.fused && !add_post(s - 1)) goto bad;
+        if (st.split || (st.fused && !st.fused_local)) {
+            if (st.split) close();
+            open(pack, {r_prev, r_pack}, true, true, true);
+            pack.mark_prev = st.fused;
+            if (st.fused && !add_post(s - 1)) return false;
         }
         st.pack_b = (int)pieces.size();
-        for (int i = first_pack; i < sp.pre_count; ++i)
-            if (!add(dp->copies[sp.pre_begin + i], 0)) goto bad;
+        if (!add_range(r_pack, 0)) return false;
         ds.close_group();
         st.pack_n = (int)pieces.size() - st.pack_b;
         st.pack_bytes = span(st.pack_b);
         st.pre_n = st.local_n + st.pack_n;
+        close();
         st.post_b = (int)pieces.size();
-        st.post_n = 0;
-        st.post_bytes = 0;
-        launch_chunk({r_post}, true);
-        if (!st.deferred && !add_post(s)) goto bad;
-    }
-    // order of a launch's local pieces (workgroup i copies piece i): by destination address.
-    // The workgroups in flight at any moment then write a few consecutive segments instead of
-    // one piece in each of dozens of scattered slots -- 7-10 % shorter all-to-many launches
-    // (DRAM row locality of the write stream; message or source order measured slower,
-    // profiles/r02/piece_order/; so did dealing each XCD its own eighth, 3-8 %,
-    // profiles/r04/xcd_order/).  Local pieces carry no displacement fix-ups and a launch's
-    // pieces are independent, so any order is valid.
-    // Unpack pieces (source in staging, patched by the device scan) are ordered by their
-    // destination too, with their fix-ups renumbered.
-    {
-        auto key_less = [](const xgk::DCopy &x, const xgk::DCopy &y) { return x.dst < y.dst; };
-        for (const StepR &st : p->steps)
-            std::stable_sort(pieces.begin() + st.local_b, pieces.begin() + st.local_b + st.local_n, key_less);
-        std::vector<int> where(pieces.size(), -1);      // old index -> its fix-up
-        for (size_t f = 0; f < ds.fix.size(); ++f) where[ds.fix[f].piece] = (int)f;
-        for (const StepR &st : p->steps) {
-            if (st.post_n < 2) continue;
-            std::vector<int> idx(st.post_n);
-            for (int i = 0; i < st.post_n; ++i) idx[i] = st.post_b + i;
-            std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return pieces[x].dst < pieces[y].dst; });
-            std::vector<xgk::DCopy> sorted(st.post_n);
-            for (int i = 0; i < st.post_n; ++i) sorted[i] = pieces[idx[i]];
-            for (int i = 0; i < st.post_n; ++i) {
-                const int f = where[idx[i]];
-                if (f >= 0) ds.fix[f].piece = st.post_b + i;
-            }
-            std::copy(sorted.begin(), sorted.end(), pieces.begin() + st.post_b);
+        if (!st.deferred) {
+            open(post, {r_post}, true, false, false);
+            if (!add_post(s)) return false;
+            close();
         }
+        // issue order.  A fused launch ends the previous step, so it goes before anything of this
+        // one.  The packs feed the RCCL group (the critical path), the local part does not: by
+        // default the local part forks after the pack launch, so it overlaps the transfer instead
+        // of sharing HBM with the packs (XG_SPLIT_AFTER_PACK=0: both at once, as in round 2)
+        std::vector<CopyLaunch> &tab = p->launches;
+        auto push = [&](const CopyLaunch &l) {
+            if (l.n > 0) tab.push_back(l);
+        };
+        const bool pack_first = st.fused || c->split_after_pack;
+        st.l_b = (int)tab.size();
+        push(stage);
+        if (pack_first) push(pack);
+        push(local);
+        if (!pack_first) push(pack);
+        st.l_rccl = (int)tab.size();
+        push(post);
+        st.l_e = (int)tab.size();
+        return true;
     }
+};
+
+static bool build_tables(xg_plan *p, const xg_devplan *dp, std::vector<xgk::DCopy> &pieces, DisplScan &ds)
+{
+    TableBuilder tb{p, dp, pieces, ds};
+    for (int s = 0; s < dp->nsteps; ++s)
+        if (!tb.step(s)) return false;
+    return true;
+}
+
+// Order of a launch's local pieces (workgroup i copies piece i): by destination address.
+// The workgroups in flight at any moment then write a few consecutive segments instead of
+// one piece in each of dozens of scattered slots -- 7-10 % shorter all-to-many launches
+// (DRAM row locality of the write stream; message or source order measured slower,
+// profiles/r02/piece_order/; so did dealing each XCD its own eighth, 3-8 %,
+// profiles/r04/xcd_order/).  Local pieces carry no displacement fix-ups and a launch's
+// pieces are independent, so any order is valid.
+// Unpack pieces (source in staging, patched by the device scan) are ordered by their
+// destination too, with their fix-ups renumbered.
+static void order_pieces(const xg_plan *p, std::vector<xgk::DCopy> &pieces, DisplScan &ds)
+{
+    auto key_less = [](const xgk::DCopy &x, const xgk::DCopy &y) { return x.dst < y.dst; };
+    for (const StepR &st : p->steps)
+        std::stable_sort(pieces.begin() + st.local_b, pieces.begin() + st.local_b + st.local_n, key_less);
+    std::vector<int> where(pieces.size(), -1);      // old index -> its fix-up
+    for (size_t f = 0; f < ds.fix.size(); ++f) where[ds.fix[f].piece] = (int)f;
+    for (const StepR &st : p->steps) {
+        if (st.post_n < 2) continue;
+        std::vector<int> idx(st.post_n);
+        for (int i = 0; i < st.post_n; ++i) idx[i] = st.post_b + i;
+        std::stable_sort(idx.begin(), idx.end(), [&](int x, int y) { return pieces[x].dst < pieces[y].dst; });
+        std::vector<xgk::DCopy> sorted(st.post_n);
+        for (int i = 0; i < st.post_n; ++i) sorted[i] = pieces[idx[i]];
+        for (int i = 0; i < st.post_n; ++i) {
+            const int f = where[idx[i]];
+            if (f >= 0) ds.fix[f].piece = st.post_b + i;
+        }
+        std::copy(sorted.begin(), sorted.end(), pieces.begin() + st.post_b);
+    }
+}
+
+// Each launch's dispatches.  A launch of more than 1.5 x launch_max bytes goes as back-to-back
+// kernel dispatches of about launch_max bytes each (its pieces are independent: the same step,
+// a few more kernel boundaries).  P256 A32 -d 4 MiB m1 / m2 (one 32 GiB step, 1 M pieces):
+// 12.6 -> 11.0 ms at 512 MiB per dispatch, 11.5 at 128 MiB; cutting by piece count instead
+// hurt steps of small pieces (profiles/r02/launch_split/).  Every count of launches
+// (xg_plan_launches, the kernel-timing sessions) counts these dispatches, as rocprofv3 does.
+static void cut_launches(xg_plan *p)
+{
+    const int64_t cap = p->ctx->launch_max;
+    const int64_t *pre = p->plen.data();        // prefix sums of the piece lengths
+    for (CopyLaunch &l : p->launches) {
+        const int end = l.b + l.n;
+        l.cut = (int)p->cuts.size();
+        p->cuts.push_back(l.b);
+        for (int o = l.b; cap > 0 && l.bytes > cap + cap / 2 && o < end;) {
+            // the first piece boundary at least cap bytes past o (lower_bound may return end + 1
+            // when fewer than cap bytes remain: clamp), then no runt dispatch at the end
+            int e = (int)(std::lower_bound(pre + o + 1, pre + end + 1, pre[o] + cap) - pre);
+            if (e > end) e = end;
+            if (end - e < 16 || pre[end] - pre[e] < cap / 2) e = end;
+            if (e < end) p->cuts.push_back(e);
+            o = e;
+        }
+        p->cuts.push_back(end);
+        l.ndisp = (int)p->cuts.size() - 1 - l.cut;
+    }
+}
+
+// Chains (xg_plan::chain_end).  A chain step: no engine segment's, no RCCL, no unpack, no
+// barrier, and every launch of it on the main stream with a kernel that can stamp its start.
+static bool find_chains(xg_plan *p)
+{
+    auto chain_step = [&](int s) {
+        const StepR &st = p->steps[s];
+        if (p->seg_of[s] >= 0 || st.l_e == st.l_b || st.l_rccl != st.l_e || st.p2p_n || st.sync_after ||
+            st.pack_n || st.deferred)
+            return false;
+        for (int i = st.l_b; i < st.l_e; ++i) {
+            const CopyLaunch &l = p->launches[i];
+            if (l.side || l.mark_prev || !l.stamps) return false;
+        }
+        return true;
+    };
+    bool any = false;
+    for (int s = 0; s < p->nsteps;) {
+        int e = s;
+        while (e < p->nsteps && chain_step(e)) ++e;
+        if (e - s >= 2) {
+            p->chain_end[s] = e;
+            any = true;
+        }
+        s = e > s ? e : s + 1;
+    }
+    return any;
+}
+
+// Device half of a plan load: the piece table, the fork / join events, the displacement scan,
+// the engine segments and the chain stamps.  On an error the caller frees the plan
+// (xg_plan_free takes a half-loaded one: every handle starts null).
+static int plan_upload(xg_plan *p, const std::vector<xgk::DCopy> &pieces, DisplScan &ds)
+{
+    int rc;
+    if (p->npieces) {
+        HIPCHK(hipMalloc(&p->d_pieces, sizeof(xgk::DCopy) * pieces.size()));
+        HIPCHK(hipMemcpy(p->d_pieces, pieces.data(), sizeof(xgk::DCopy) * pieces.size(), hipMemcpyHostToDevice));
+    }
+    p->need_mark.assign(p->nsteps, 1);
+    p->fork.assign(p->nsteps, nullptr);
+    p->join.assign(p->nsteps, nullptr);
+    for (int s = 0; s < p->nsteps; ++s)
+        for (int i = p->steps[s].l_b; i < p->steps[s].l_rccl; ++i)
+            if (p->launches[i].side) {
+                HIPCHK(hipEventCreateWithFlags(&p->fork[s], hipEventDisableTiming));
+                HIPCHK(hipEventCreateWithFlags(&p->join[s], hipEventDisableTiming));
+            }
+    HIPCHK(hipMalloc(&p->d_gstamp, 8 * ((size_t)p->nsteps + 1)));
+    if ((rc = run_displ_scan(p, ds)) || (rc = build_segments(p, pieces))) return rc;
+    p->chain_end.assign(p->nsteps, 0);
+    if (p->ctx->step_chain && find_chains(p)) HIPCHK(hipMalloc(&p->d_cstamp, 8 * (size_t)p->nsteps));
+    return XG_OK;
+}
+
+extern "C" int xg_plan_load(xg_ctx *c, xg_regions *r, const xg_devplan *dp, xg_plan **out)
+{
+    if (!c || !r || !dp || !out) return XG_EARG;
+    if (dp->ngpus != c->nranks || dp->gpu != c->rank) {
+        fprintf(stderr, "xg_plan_load: plan for gpu %d/%d loaded on rank %d/%d\n", dp->gpu, dp->ngpus, c->rank,
+                c->nranks);
+        return XG_EARG;
+    }
+    for (int i = 0; i < XG_NBUF; ++i)
+        if (dp->region_bytes[i] > r->bytes[i]) {
+            fprintf(stderr, "xg_plan_load: region %d too small (%lld < %lld)\n", i, (long long)r->bytes[i],
+                    (long long)dp->region_bytes[i]);
+            return XG_EARG;
+        }
+    HIPCHK(hipSetDevice(c->device));
+    xg_plan *p = new xg_plan();
+    p->ctx = c; p->reg = r; p->nsteps = dp->nsteps; p->variant = c->variant; p->id = next_plan_id();
+    std::vector<xgk::DCopy> pieces;
+    DisplScan ds;
+    if (!step_forms(p, dp) || (p->streaming = plan_streams(p, dp), !build_tables(p, dp, pieces, ds))) {
+        fprintf(stderr, "xg_plan_load: copy or p2p descriptor outside its region\n");
+        delete p;
+        return XG_EARG;
+    }
+    order_pieces(p, pieces, ds);
     p->npieces = (int)pieces.size();
-    wave_at.resize(pieces.size() + 1, 0);
-    p->wave_at.swap(wave_at);
     p->plen.assign(pieces.size() + 1, 0);
     for (size_t i = 0; i < pieces.size(); ++i) p->plen[i + 1] = p->plen[i] + pieces[i].len;
-    if ((rc = plan_upload(p, pieces, ds))) {
+    cut_launches(p);
+    if (const int rc = plan_upload(p, pieces, ds)) {
         xg_plan_free(p);        // frees whatever the upload got to
         return rc;
     }
-    for (int s = 0; s < p->nsteps; ++s) {
-        const StepR &st = p->steps[s];
-        if (p->seg_of[s] >= 0) {
-            p->nlaunch += p->segs[p->seg_of[s]].s0 == s;
-            continue;
-        }
-        // kernel dispatches, as enqueue_pre / enqueue_post issue them (launch_cuts)
-        auto D = [&](int b, int n, int64_t bytes) { return n > 0 ? launch_dispatches(p, b, n, bytes) : 0; };
-        p->nlaunch += D(st.stage_b, st.stage_n, st.stage_bytes);
-        if (st.fused) {
-            const StepR &pv = p->steps[s - 1];
-            p->nlaunch += D(pv.post_b, pv.post_n + (st.fused_local ? st.local_n : 0) + st.pack_n,
-                            pv.post_bytes + (st.fused_local ? st.local_bytes : 0) + st.pack_bytes);
-        }
-        if (st.split)
-            p->nlaunch += D(st.local_b, st.local_n, st.local_bytes) + (st.fused ? 0 : D(st.pack_b, st.pack_n, st.pack_bytes));
-        else if (!st.fused)
-            p->nlaunch += D(st.local_b, st.pre_n, st.local_bytes + st.pack_bytes);
-        if (!st.deferred) p->nlaunch += D(st.post_b, st.post_n, st.post_bytes);
-    }
-    {
-        int64_t run = 0;
-        for (const StepR &st : p->steps) run += st.stage_bytes + st.local_bytes + st.pack_bytes + st.post_bytes;
-        // a one-GPU run of several small launches is bound by launching them, not by their
-        // bytes: replayed as one graph (README TAM chains 17-19 -> 15-16 us,
-        // profiles/r03/readme_cli/summary.txt).  Multi-GPU and virtual runs stay launched:
-        // graphs of RCCL and cross-stream nodes replayed 1.1-5x slower (profiles/r03/hybrid/)
-        p->graph_auto = c->nranks == 1 && !c->virt && run <= ((int64_t)16 << 20);
-    }
-    p->chain_end.assign(p->nsteps, 0);
-    if (c->step_chain) {
-        // a chain step: its stage copies (TAM) and/or its local copies, each one launch
-        // of a variant that can stamp its start, and nothing else
-        auto one_launch = [&](int s) {
-            const StepR &st = p->steps[s];
-            auto stamps = [&](int64_t bytes, bool reread) {
-                const int v = copy_variant(p, bytes, reread);
-                return v == 1 || v == 6;
-            };
-            return p->seg_of[s] < 0 && !st.split && !st.fused && !st.deferred && !st.p2p_n && !st.pack_n &&
-                   !st.post_n && !st.sync_after && (st.local_n > 0 || st.stage_n > 0) &&
-                   (!st.local_n || stamps(st.local_bytes, st.stage_fused)) && (!st.stage_n || stamps(st.stage_bytes, true));
-        };
-        bool any = false;
-        for (int s = 0; s < p->nsteps;) {
-            int e = s;
-            while (e < p->nsteps && one_launch(e)) ++e;
-            if (e - s >= 2) {
-                p->chain_end[s] = e;
-                any = true;
-            }
-            s = e > s ? e : s + 1;
-        }
-        if (any) {
-            const hipError_t e = hipMalloc(&p->d_cstamp, 8 * (size_t)p->nsteps);
-            if (e != hipSuccess) {
-                p->d_cstamp = nullptr;
-                fprintf(stderr, "xg: HIP error %s: chain stamps\n", hipGetErrorString(e));
-                xg_plan_free(p);
-                return XG_EHIP;
-            }
-        }
-    }
+    // kernel dispatches per run: an engine segment is one, every other step its table entries'
+    p->nlaunch = (int)p->segs.size();
+    each_launch(p, [&](const CopyLaunch &l) { p->nlaunch += l.ndisp; });
+    int64_t run = 0;
+    for (const StepR &st : p->steps) run += st.stage_bytes + st.local_bytes + st.pack_bytes + st.post_bytes;
+    // a one-GPU run of several small launches is bound by launching them, not by their
+    // bytes: replayed as one graph (README TAM chains 17-19 -> 15-16 us,
+    // profiles/r03/readme_cli/summary.txt).  Multi-GPU and virtual runs stay launched:
+    // graphs of RCCL and cross-stream nodes replayed 1.1-5x slower (profiles/r03/hybrid/)
+    p->graph_auto = c->nranks == 1 && !c->virt && run <= ((int64_t)16 << 20);
     *out = p;
     return XG_OK;
-bad:
-    fprintf(stderr, "xg_plan_load: copy or p2p descriptor outside its region\n");
-    delete p;
-    return XG_EARG;
 }
 
 extern "C" int xg_plan_free(xg_plan *p)

@@ -3,8 +3,9 @@
 // macros, and the helpers more than one of them calls.  gfx950 only.
 //
 //   ctx.hip        context (streams, communicator), HBM regions, fill / verify / span checksums
-//   plan_load.hip  xg_plan_load: piece table, launch forms, engine segments, displacement scan
-//   exec.hip       execution: per-step launches + RCCL groups, chains, engine, graph, armed runs
+//   plan_load.hip  xg_plan_load: piece table, copy-launch table, engine segments, displacement scan
+//   exec.hip       execution: walks each step's launch-table entries, RCCL groups, chains, engine,
+//                  graph, armed runs
 //   virtual.hip    a whole G-GPU job on one device (test hook)
 //   measure.hip    kernel-timing sessions and the RCCL p2p microbenchmark
 #pragma once
@@ -128,7 +129,7 @@ struct xg_ctx {
     int solo_waves;            // waves per rail: 16 (a workgroup) or 1
     int64_t launch_max;        // copy launches above this many bytes go as back-to-back launches of ~this size
     int64_t wave_min;          // cross-GPU steps' plain copy launches of >= this many bytes (and <= kWaveMax)
-                               // run copy_kernel_w (launch_chunk)
+                               // run copy_kernel_w (TableBuilder::open)
     int wave_grid;             // copy_kernel_w workgroups resident at once (occupancy x CUs)
     int wave_kib;              // XG_WAVE_KIB: copy_kernel_w piece KiB forced (2 / 4 / 8), 0 = by launch bytes
     int cus;                   // compute units
@@ -141,7 +142,7 @@ struct xg_ctx {
     int split_after_pack;      // 1: a split step's local part forks after its pack launch
     int graph;                 // hipGraph replay of multi-launch runs: 1 always, 0 never, -1 latency-bound one-GPU runs
     double wall_hz;            // wall_clock64() rate
-    int variant;            // copy kernel variant (launch_copy)
+    int variant;            // copy kernel variant (copy_variant in plan_load.hip)
     int engine_occ;            // co-resident step-engine workgroups the device admits (plan load caps W)
     // kernel timing session (xg_ktime_begin/end): 1 = an event pair around every
     // copy launch, 2 = one pair around the whole session on the main stream
@@ -159,26 +160,50 @@ struct xg_regions {
     bool owned[XG_NBUF];    // hipMalloc'd here (freed, poisoned at creation); false: the caller's memory (xg_regions_adopt)
 };
 
+// One copy launch of a run, decided once by xg_plan_load (build_tables in plan_load.hip: the only
+// place that turns a step's form -- split, fused, fused_local, stage_fused, deferred, self_local --
+// into launches) and never changed after: execution, the launch counts and chain eligibility all
+// read the table.
+struct CopyLaunch {
+    int b = 0, n = 0;                // pieces [b, b + n) of the plan's piece table
+    int64_t bytes = 0;               // bytes they copy (read + written once)
+    int kib = 0;                     // 2 / 4 / 8: copy_kernel_w<kib> over pieces of <= kib KiB; 0: copy_kernel_g<4>
+    bool nt = false;                 // copy_kernel_g<4, true>: non-temporal loads and stores
+    bool stamps = false;             // its kernel can stamp its start (a chain step's launch must)
+    bool side = false;               // runs on the side stream: fork event before it, join event after it
+    bool mark_prev = false;          // holds the previous step's unpacks: that step's mark goes right behind it
+    int cut = 0, ndisp = 1;          // its dispatches (launches above 1.5 x launch_max go as several):
+                                     // dispatch k = pieces [cuts[cut + k], cuts[cut + k + 1]) of xg_plan::cuts
+};
+
 struct StepR {
-    // Launches of one step (piece ranges in the plan's piece table):
-    //   stage (TAM rank-local copies), then local gather/scatter + packs into staging
-    //   (one launch; a step with cross-GPU ops runs its local part on the side stream
-    //   beside the packs and the RCCL group: split), the RCCL group, the unpacks.
+    // Piece ranges of one step's parts in the plan's piece table: stage (TAM rank-local
+    // copies), local gather/scatter, packs into staging, unpacks out of it.  How the parts
+    // launch is the step's run of the launch table (below).
+    //   split: a step with cross-GPU ops runs its local part on the side stream beside the
+    //   packs and the RCCL group.
     //   fused: this step's packs go in ONE launch with the previous step's unpacks
     //   (deferred there); a pack only fills staging and delivers nothing, so every
     //   message of this step is still delivered after every one of the previous step.
     // call_b / call_n: the step's RCCL calls in the plan's call list (xg_devplan_step_calls);
     // p2p_n of them are send/recv (one group), sync_after: the last is the in-loop barrier
-    int stage_b, stage_n, local_b, local_n, pack_b, pack_n, post_b, post_n, call_b, call_n, p2p_n, sync_after;
-    int groups;                      // RCCL groups of the step: 1, or 2 for a relay step (XG_CALL_FENCE between)
-    int posts;                       // request posts of this GPU's ranks in the step (xg_stepplan.posts)
-    int pre_n;                       // local_n + pack_n
-    int64_t stage_bytes, local_bytes, pack_bytes, post_bytes;   // bytes copied by each part (read + written once)
-    bool split, fused, deferred;
-    bool self_local;                 // the local copies travel in the RCCL group as self send/recv (XG_SELF_MAX)
-    bool fused_local;                // fused, and the local copies join that launch (small, hazard-free)
-    bool stage_fused;                // the stage copies join the step's local (+ pack) launch: none of the
+    int stage_b = 0, stage_n = 0, local_b = 0, local_n = 0, pack_b = 0, pack_n = 0, post_b = 0, post_n = 0;
+    int call_b = 0, call_n = 0, p2p_n = 0, sync_after = 0;
+    int groups = 1;                  // RCCL groups of the step: 1, or 2 for a relay step (XG_CALL_FENCE between)
+    int posts = 0;                   // request posts of this GPU's ranks in the step (xg_stepplan.posts)
+    int pre_n = 0;                   // local_n + pack_n
+    int64_t stage_bytes = 0, local_bytes = 0, pack_bytes = 0, post_bytes = 0;   // bytes copied by each part (read + written once)
+    bool split = false, fused = false, deferred = false;
+    bool self_local = false;         // the local copies travel in the RCCL group as self send/recv (XG_SELF_MAX)
+    bool fused_local = false;        // fused, and the local copies join that launch (small, hazard-free)
+    bool stage_fused = false;        // the stage copies join the step's local (+ pack) launch: none of the
                                      // other pre copies meets their bytes (xg_step_stage_meets_rest)
+    // The step's launches: entries [l_b, l_e) of xg_plan::launches, in issue order -- the stage
+    // launch, the fused launch (previous unpacks + packs), then the packs and the forked local
+    // part (XG_SPLIT_AFTER_PACK decides which goes first) or the one local + pack launch; the
+    // RCCL group goes before entry l_rccl; the unpacks follow it, unless deferred into the next
+    // step's fused launch.  (An engine segment's steps never run theirs.)
+    int l_b = 0, l_rccl = 0, l_e = 0;
 };
 
 // A run of >= 2 consecutive GPU-local steps (no RCCL op, no in-loop barrier, no
@@ -203,68 +228,77 @@ struct EngSeg {
 };
 
 struct xg_plan {
-    xg_ctx *ctx;
-    xg_regions *reg;
-    int nsteps;
-    xgk::DCopy *d_pieces;
-    int npieces;
+    xg_ctx *ctx = nullptr;
+    xg_regions *reg = nullptr;
+    int nsteps = 0;
+    xgk::DCopy *d_pieces = nullptr;
+    int npieces = 0;
     std::vector<StepR> steps;
-    std::vector<xg_call> calls;       // every step's RCCL calls, as xg_devplan_step_calls lists them
-    std::vector<int32_t> call_begin;  // nsteps + 1: where each step's calls start
-    std::vector<hipEvent_t> fork, join;   // per split step: main -> side, side -> main
-    int variant;
-    bool streaming;                // one run copies more than the Infinity Cache holds (read + write)
+    std::vector<xg_call> calls;             // every step's RCCL calls, as xg_devplan_step_calls lists them
+    std::vector<int32_t> call_begin;        // nsteps + 1: where each step's calls start
+    std::vector<CopyLaunch> launches;       // every step's copy launches (StepR::l_b .. l_e), fixed at load
+    std::vector<int> cuts;                  // their dispatches' piece boundaries (CopyLaunch::cut)
+    std::vector<hipEvent_t> fork, join;     // per step with a side-stream launch: main -> side, side -> main
+    int variant = 0;
+    bool streaming = false;                 // one run copies more than the Infinity Cache holds (read + write)
     // step engine segments
-    std::vector<int> seg_of;       // per step: index into segs, or -1
+    std::vector<int> seg_of;                // per step: index into segs, or -1
     std::vector<EngSeg> segs;
-    int *d_sb;
-    xgk::DCopy *d_epieces;         // every segment's work units, step-major
-    xgk::EngineState *d_engine;    // state (16 B, zeroed at load) followed by stamps: rail r's of step
-                                   // s at [r * nsteps + s] (grid segments: rail 0)
-    int stamp_rails;               // rails the stamp area holds
-    unsigned engine_base;          // barrier tickets taken by earlier launches (wraps)
-    bool engine_reset;             // zero the state before the next launch
-    xgk::Doorbell *db;             // host-pinned doorbell of armed runs (single-segment plans), or null
-    std::vector<unsigned long long> solo_desc;   // solo segments' packed pieces (host copy)
-    unsigned long long *d_solo;
-    unsigned epoch;                // armed launches so far
+    int *d_sb = nullptr;
+    xgk::DCopy *d_epieces = nullptr;        // every segment's work units, step-major
+    xgk::EngineState *d_engine = nullptr;   // state (16 B, zeroed at load) followed by stamps: rail r's of step
+                                            // s at [r * nsteps + s] (grid segments: rail 0)
+    int stamp_rails = 1;                    // rails the stamp area holds
+    unsigned engine_base = 0;               // barrier tickets taken by earlier launches (wraps)
+    bool engine_reset = false;              // zero the state before the next launch
+    xgk::Doorbell *db = nullptr;            // host-pinned doorbell of armed runs (single-segment plans), or null
+    std::vector<unsigned long long> solo_desc;  // solo segments' packed pieces (host copy)
+    unsigned long long *d_solo = nullptr;
+    unsigned epoch = 0;                     // armed launches so far
     // staging displacements of the packed segments, computed on the device at load
-    int64_t *d_disp;
-    int ndisp;
-    int nlaunch;                   // kernel launches per run (copies + engine), RCCL's aside
-    bool rec_ev;                   // xg_plan_run is marking steps (fused launches mark the previous step's end)
+    int64_t *d_disp = nullptr;
+    int ndisp = 0;
+    int nlaunch = 0;                        // kernel launches per run (copies + engine), RCCL's aside
+    bool rec_ev = false;                    // xg_plan_run is marking steps (fused launches mark the previous step's end)
     // chains: runs of >= 2 consecutive steps that are each ONE local copy launch, or a TAM
     // stage launch and/or a local launch (outside engine segments, no RCCL, no barrier).  xg_plan_run times them with no
     // mark between launches: launch t+1 stamps its start = step t's completion, a clock kernel
     // closes the chain, the chain's mark after it anchors the stamps.  chain_end[s] = end of s's chain (s = its
     // first step), 0 elsewhere.
     std::vector<int> chain_end;
-    unsigned long long *d_cstamp;  // nsteps wall-clock stamps of chained steps
-    std::vector<int64_t> plen;     // prefix sums of the piece lengths (npieces + 1), host side
-    std::vector<char> wave_at;     // npieces + 1: at the first piece of a copy_kernel_w launch, its
-                                   // piece KiB (2 / 4 / 8: the J of copy_kernel_w<J>); else 0
+    unsigned long long *d_cstamp = nullptr;  // nsteps wall-clock stamps of chained steps
+    std::vector<int64_t> plen;              // prefix sums of the piece lengths (npieces + 1), host side
     // hipGraph replay (XG_GRAPH=1): the launches of one xg_plan_enqueue / one timed xg_plan_run,
     // captured at first use and replayed after (a launch-bound multi-step run then costs one
     // graph launch of host time instead of a launch, an event and an RCCL group per step)
-    hipGraphExec_t g_enq, g_run;
+    hipGraphExec_t g_enq = nullptr, g_run = nullptr;
     // step marks: mark(i) has a one-lane clock_kernel write the wall clock to d_gstamp[i + 1]
     // (i = -1: the start) once everything before it on the stream is done.  Not timing events:
     // an event record left the device idle ~4.7 us per step against ~2.1 us for the stamp
     // (profiles/r04/stamp_marks/), and captured events are not re-recorded by a graph replay on
     // this stack (tools/graph_probe.hip), so eager runs, graph replays and virtual jobs all stamp
-    unsigned long long *d_gstamp;
-    std::vector<char> need_mark;   // per step: an eager or captured run marks it (xg_plan_set_step_marks;
-                                   // default all) -- engine segments and chains mark their last step always
-    bool graph_auto;               // XG_GRAPH unset: this plan replays as a graph (latency-bound, one GPU)
-    bool local_only;               // test hook (xg_plan_set_local_only): a virtual GPU runs its share alone,
-                                   // its RCCL calls and in-loop barriers left out
-    uint64_t id;                   // unique per loaded plan (keys the virtual runner's graphs)
+    unsigned long long *d_gstamp = nullptr;
+    std::vector<char> need_mark;            // per step: an eager or captured run marks it (xg_plan_set_step_marks;
+                                            // default all) -- engine segments and chains mark their last step always
+    bool graph_auto = false;                // XG_GRAPH unset: this plan replays as a graph (latency-bound, one GPU)
+    bool local_only = false;                // test hook (xg_plan_set_local_only): a virtual GPU runs its share alone,
+                                            // its RCCL calls and in-loop barriers left out
+    uint64_t id = 0;                        // unique per loaded plan (keys the virtual runner's graphs)
     struct VGraph {
         std::vector<uint64_t> ids;
-        bool rccl;
-        hipGraphExec_t exec;
-    } vg;                          // plans[0] of a virtual job: the job's captured run
+        bool rccl = false;
+        hipGraphExec_t exec = nullptr;
+    } vg;                                   // plans[0] of a virtual job: the job's captured run
 };
+
+// Every copy launch one run issues, in issue order (an engine segment's steps issue none).
+template <class F>
+static void each_launch(const xg_plan *p, F f)
+{
+    for (int s = 0; s < p->nsteps; ++s)
+        if (p->seg_of[s] < 0)
+            for (int i = p->steps[s].l_b; i < p->steps[s].l_e; ++i) f(p->launches[i]);
+}
 
 // Capture what `body` enqueues on `stream` into a graph and instantiate it.  The stream
 // leaves capture mode on every path; on failure nothing is kept.
@@ -309,19 +343,6 @@ static inline int wave_kib_for(int64_t bytes, int cus)
     return 2;
 }
 
-// The copy kernel variant of a launch moving `bytes` (launch_copy).  Variant 0 picks
-// non-temporal loads/stores (6) when the bytes cannot come back from the 256 MiB
-// Infinity Cache: a launch whose own source + destination exceed it, or a launch of
-// >= kNtStream bytes in a plan whose run copies more than it (every step then finds
-// its bytes evicted by the steps before) -- unless what it writes is read again at
-// once (`reread`: packs feeding RCCL, TAM stage copies), which then may still find
-// it in the cache; plain (1) otherwise.
-static inline int copy_variant(const xg_plan *p, int64_t bytes, bool reread = false)
-{
-    if (p->variant) return p->variant;
-    return bytes >= kNtMin || (!reread && p->streaming && bytes >= kNtStream) ? 6 : 1;
-}
-
 // RCCL writes its log -- and, under NCCL_DEBUG=WARN/VERSION, a version banner at
 // communicator creation -- to stdout unless NCCL_DEBUG_FILE says otherwise; stdout
 // here carries the reference's report (bin/test, bin/pt2pt_test) and bench.py's JSON
@@ -358,7 +379,6 @@ struct StdoutToStderr {
 int mark(xg_plan *p, int i, hipStream_t stream);
 int read_marks(const xg_plan *p, std::vector<unsigned long long> &gs);
 double mark_elapsed(const xg_plan *p, int i, const std::vector<unsigned long long> &gs);
-int launch_dispatches(const xg_plan *p, int b, int n, int64_t bytes);
-int enqueue_pre(xg_plan *p, int s, hipStream_t stream, hipStream_t side);
+int enqueue_pre(xg_plan *p, int s, hipStream_t stream, hipStream_t side, unsigned long long *start = nullptr);
 int enqueue_post(xg_plan *p, int s, hipStream_t stream);
 int launch_seg(xg_plan *p, const EngSeg &g, hipStream_t stream, bool armed = false);

@@ -3,7 +3,8 @@
 #include "rt.h"
 
 // Every GPU of a virtual job (xg_init_virtual), step by step on plans[0]'s
-// stream: all pre copies (or a GPU's whole engine segment, at its first step:
+// stream: all pre copies (enqueue_pre: each GPU's launch-table entries up to its RCCL
+// group, the same walk a real rank makes; or a GPU's whole engine segment, at its first step:
 // its steps touch only that GPU's regions and hold none of its cross-GPU ops,
 // so running them together is what a real GPU does too), then each RCCL
 // send/recv pair as one device copy (sends of g to h matched in order with h's
