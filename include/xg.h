@@ -171,6 +171,10 @@ int xg_plan_launches(const xg_plan *p);
  * *max_pieces_per_wave = the largest ceil(pieces / (4 x workgroups)) over those launches, a
  * launch of n pieces starting min(grid, ceil(n / 4)) workgroups of 4 waves.  Either may be NULL. */
 int xg_plan_wave_launches(const xg_plan *p, int *grid, int *max_pieces_per_wave);
+/* The copy launches that run copy_kernel_s, the shifted piece copy: in a plan whose device plan
+ * has XG_DP_RAGGED, every launch with a piece whose source, destination or length is off the 16-B
+ * grid (none with XG_RAGGED_COPY=0, and none in any other plan). */
+int xg_plan_shift_launches(const xg_plan *p);
 /* Staging displacements of the plan's packed segments as computed on the device
  * at load (one wavefront prefix scan per step and direction: the alltoallw
  * translate of mpi_test.c:233-302).  out == NULL: returns their number. */
@@ -275,6 +279,16 @@ int xg_run_method(xg_ctx *ctx, int method, int procs, int cb_nodes, int data_siz
 int xg_exchange(xg_ctx *ctx, int method, int procs, int cb_nodes, int data_size, const int *rank_list,
                 int comm_size, void *send, void *recv, xg_timer *timers, int iter, int ntimes,
                 const xg_run_opts *opts, int64_t *bad_slots, char *err, size_t errlen);
+/* xg_exchange with a length per (rank, aggregator index) pair in place of data_size: the
+ * alltoallv-shaped exchange.  lens[r * cb_nodes + a] as xg_sched_build_v takes it (methods 1..14
+ * and 17..20 when the lengths differ); the buffers are laid out densely, as that schedule's
+ * xg_send_offset / xg_recv_offset / xg_seg_offset / xg_slot_offset / xg_region_bytes say.  Every
+ * rank must pass the same matrix: it is part of what the ranks compare before the first RCCL call
+ * (XG_EARG on every rank when they differ).  The payload check takes each span's length from
+ * xg_delivery_lens. */
+int xg_exchange_v(xg_ctx *ctx, int method, int procs, int cb_nodes, const int64_t *lens, const int *rank_list,
+                  int comm_size, void *send, void *recv, xg_timer *timers, int iter, int ntimes,
+                  const xg_run_opts *opts, int64_t *bad_slots, char *err, size_t errlen);
 
 /* The operators under the reference's names (mpi_test.c line of the original). */
 #define XG_METHOD_DECL(name)                                                                     \

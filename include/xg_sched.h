@@ -93,7 +93,27 @@ xg_sched *xg_sched_build(int method, int procs, int cb_nodes, int64_t data_size,
 xg_sched *xg_sched_build_iter(int method, int procs, int cb_nodes, int64_t data_size, int comm_size,
                               const int *rank_list, int ntimes, int proc_node, int barrier_type,
                               int64_t eager_limit, int iter, char *err, size_t errlen);
+/* The same with a length per (rank, aggregator) pair, as MPI_Alltoallv counts would give them.
+ * lens[r * cb_nodes + a]: bytes between logical rank r and aggregator index a (a2m: r sends them to
+ * rank_list[a]; m2a: rank_list[a] sends them to r).  >= 0; 0 = an empty segment.
+ * A matrix whose entries all equal d IS the schedule xg_sched_build_iter builds with d (messages,
+ * steps, traces, layout, device plans; xg_sched_ragged is 0).  Otherwise the schedule is RAGGED:
+ * every post and self copy of the method carries its own segment's length, and the layout is dense
+ * -- a rank's SEND part is its segments back to back in segment order, its RECV part its slots back
+ * to back in slot order (xg_seg_offset / xg_slot_offset: prefix sums of the lengths).  A zero-length
+ * segment behaves as zero-length messages do in the uniform schedules (Alltoallw and the scattered
+ * methods post nothing for it, the pairwise methods a 0-byte Sendrecv).  Methods 1..14 and 17..20;
+ * m15 / m16 (TAM) return NULL for a matrix that is not uniform. */
+xg_sched *xg_sched_build_v(int method, int procs, int cb_nodes, const int64_t *lens, int comm_size,
+                           const int *rank_list, int ntimes, int proc_node, int barrier_type,
+                           int64_t eager_limit, int iter, char *err, size_t errlen);
 void xg_sched_free(xg_sched *s);
+int xg_sched_ragged(const xg_sched *s);                               /* 1: lengths differ */
+/* byte offset of segment `seg` inside the rank's SEND part / of slot `slot` inside its RECV part
+ * (seg / slot may equal the count: the part's size); -1 when the rank has no such part or the index
+ * is out of range */
+int64_t xg_seg_offset(const xg_sched *s, int rank, int seg);
+int64_t xg_slot_offset(const xg_sched *s, int rank, int slot);
 
 int xg_sched_nmsg(const xg_sched *s);
 const xg_msg *xg_sched_msgs(const xg_sched *s);
@@ -172,8 +192,9 @@ typedef struct {
                                          launch time out in proportion (xg_plan_run)  */
 } xg_stepplan;
 
+#define XG_DP_RAGGED 1               /* xg_devplan.flags bit 0: built from a ragged schedule */
 typedef struct {
-    int32_t gpu, ngpus, nsteps, pad;
+    int32_t gpu, ngpus, nsteps, flags;
     int64_t region_bytes[XG_NBUF];    /* send, recv, stage_send, stage_recv, scratch  */
     int32_t ncopy, np2p;
     xg_copy *copies;
@@ -378,6 +399,9 @@ int xg_verify_slots(const xg_sched *s, int ngpus, int g, xg_slot *out);
  * Returns the count; out may be NULL to query it. */
 typedef struct { int32_t src, seed, dst, slot, src_gpu, dst_gpu; int64_t send_off, recv_off; } xg_delivery;
 int xg_deliveries(const xg_sched *s, int ngpus, xg_delivery *out);
+/* The length of every delivery, in xg_deliveries' order (d for a uniform schedule, the pair's own
+ * length for a ragged one).  Returns the count; out may be NULL to query it. */
+int xg_delivery_lens(const xg_sched *s, int ngpus, int64_t *out);
 
 /* save_all_timing (mpi_test.c:2008-2066): the four per-repetition CSVs of m13,
  * <prefix>send_wait_all_times_<c>.csv, total_times, post_request_time,

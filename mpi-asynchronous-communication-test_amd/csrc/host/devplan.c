@@ -771,7 +771,7 @@ xg_devplan *xg_devplan_build_form(const xg_sched *s, int ngpus, int g, int64_t p
         oom = 1;
         goto done;
     }
-    dp->gpu = g; dp->ngpus = G; dp->nsteps = nst;
+    dp->gpu = g; dp->ngpus = G; dp->nsteps = nst; dp->flags = xg_sched_ragged(s) ? XG_DP_RAGGED : 0;
     {   /* per step, the request posts of this GPU's ranks (graph replays share their launch time
          * out by them: xg_plan_run) */
         int32_t *posts = (int32_t *)calloc((size_t)nst + 1, sizeof(int32_t));
@@ -1058,7 +1058,7 @@ int xg_verify_slots(const xg_sched *s, int ngpus, int g, xg_slot *out)
             out[n].src = s->dir == XG_A2M ? i : s->rank_list[i];
             out[n].seed = s->dir == XG_A2M ? myindex : r;
             out[n].dst = r; out[n].pad = 0;
-            out[n].off = base + (int64_t)i * s->d;
+            out[n].off = base + xg_slot_offset(s, r, i);
         }
     }
     return n;
@@ -1081,9 +1081,23 @@ int xg_deliveries(const xg_sched *s, int ngpus, xg_delivery *out)
                 q->seed = s->dir == XG_A2M ? myindex : r;
                 q->dst = r; q->slot = i;
                 q->src_gpu = xg_gpu_of(s->P, ngpus, q->src); q->dst_gpu = g;
-                q->send_off = xg_send_offset(s, ngpus, q->src) + (int64_t)q->seed * s->d;
-                q->recv_off = xg_recv_offset(s, ngpus, r) + (int64_t)i * s->d;
+                q->send_off = xg_send_offset(s, ngpus, q->src) + xg_seg_offset(s, q->src, q->seed);
+                q->recv_off = xg_recv_offset(s, ngpus, r) + xg_slot_offset(s, r, i);
             }
+        }
+    }
+    return n;
+}
+
+int xg_delivery_lens(const xg_sched *s, int ngpus, int64_t *out)
+{
+    int g, lo, hi, r, i, n = 0;
+    for (g = 0; g < ngpus; ++g) {
+        xg_block_range(s->P, ngpus, g, &lo, &hi);
+        for (r = lo; r < hi; ++r) {          /* xg_deliveries' order */
+            const int nslots = xgi_nrecv_slots(s, r);
+            for (i = 0; i < nslots; ++i, ++n)
+                if (out) out[n] = xg_slot_offset(s, r, i + 1) - xg_slot_offset(s, r, i);
         }
     }
     return n;

@@ -47,10 +47,28 @@ static op_t *push(prog_t *p)
     return o;
 }
 
+/* Ragged schedules (xg_sched_build_v): the length of the rank's send segment `seg` / receive slot
+ * `slot`, out of the P x A matrix.  a2m: segment = aggregator index, slot = source rank; m2a:
+ * segment = destination rank, slot = aggregator index.  Every post and self copy of a data segment
+ * takes its length here, whatever count the method body passes (the uniform d); posts without a
+ * segment (0-byte rounds, go-signals: seg < 0) keep their count. */
+static int64_t send_len(const prog_t *p, int seg, int64_t cnt)
+{
+    if (!p->lens || seg < 0) return cnt;
+    return p->dir == XG_A2M ? p->lens[(size_t)p->rank * p->A + seg] : p->lens[(size_t)seg * p->A + p->myindex];
+}
+
+static int64_t recv_len(const prog_t *p, int slot, int64_t cnt)
+{
+    if (!p->lens || slot < 0) return cnt;
+    return p->dir == XG_A2M ? p->lens[(size_t)slot * p->A + p->myindex] : p->lens[(size_t)p->rank * p->A + slot];
+}
+
 /* send post; tag < 0 means the reference's rank + peer on MPI_COMM_WORLD */
 static int post_send_ex(prog_t *p, int peer, int64_t cnt, int seg, int eager_ok, int isend, int comm, int tag)
 {
     op_t *o = push(p);
+    cnt = send_len(p, seg, cnt);
     o->kind = OP_SEND; o->peer = peer; o->cnt = cnt; o->idx = seg;
     o->eager_ok = (int8_t)(eager_ok || isend); o->isend = (int8_t)isend; o->comm = (int8_t)comm;
     o->tag = tag >= 0 ? tag : p->rank + peer;
@@ -61,6 +79,7 @@ static int post_send_ex(prog_t *p, int peer, int64_t cnt, int seg, int eager_ok,
 static int post_recv_ex(prog_t *p, int peer, int64_t cnt, int slot, int comm, int tag)
 {
     op_t *o = push(p);
+    cnt = recv_len(p, slot, cnt);
     o->kind = OP_RECV; o->peer = peer; o->cnt = cnt; o->idx = slot; o->comm = (int8_t)comm;
     o->tag = tag >= 0 ? tag : p->rank + peer;
     o->post = p->nposts++;
@@ -137,6 +156,7 @@ static void tstop(prog_t *p, int f) { tmark(p, f, -1); }
 static void copy_op(prog_t *p, int seg, int slot, int64_t cnt)
 {
     op_t *o = push(p);
+    cnt = send_len(p, seg, cnt);
     o->kind = OP_COPY; o->idx = seg; o->idx2 = slot; o->cnt = cnt; o->post = -1;
 }
 
@@ -363,22 +383,25 @@ static void m4_balanced(ctx_t *x)
     free(l.v);
 }
 
-/* *_alltoall_translate, mpi_test.c:233-262 (a2m) and :273-302 (m2a) */
+/* *_alltoall_translate, mpi_test.c:233-262 (a2m) and :273-302 (m2a): per peer, the count and the
+ * displacement -- kept as the segment / slot INDEX (the reference's displacement is index * d; its
+ * m2a running sum rd[rl[i]] = rd[rl[i-1]] + d is i * d as well), so that a ragged schedule, whose
+ * displacements are prefix sums, names the same segments */
 static void translate(ctx_t *x, int dir, int64_t *sc, int64_t *sd, int64_t *rc, int64_t *rd)
 {
     int i, P = x->P, A = x->A;
+    const prog_t *p = x->p;
     int64_t d = x->d;
     memset(sc, 0, sizeof(int64_t) * P); memset(sd, 0, sizeof(int64_t) * P);
     memset(rc, 0, sizeof(int64_t) * P); memset(rd, 0, sizeof(int64_t) * P);
     if (dir == XG_A2M) {
-        for (i = 0; i < A; ++i) { sd[x->rl[i]] = (int64_t)i * d; sc[x->rl[i]] = d; }
+        for (i = 0; i < A; ++i) { sd[x->rl[i]] = i; sc[x->rl[i]] = send_len(p, i, d); }
         if (x->isagg)
-            for (i = 0; i < P; ++i) { rc[i] = d; rd[i] = (int64_t)i * d; }
+            for (i = 0; i < P; ++i) { rc[i] = recv_len(p, i, d); rd[i] = i; }
     } else {
-        rd[x->rl[0]] = 0; rc[x->rl[0]] = d;
-        for (i = 1; i < A; ++i) { rd[x->rl[i]] = rd[x->rl[i - 1]] + d; rc[x->rl[i]] = d; }
+        for (i = 0; i < A; ++i) { rd[x->rl[i]] = i; rc[x->rl[i]] = recv_len(p, i, d); }
         if (x->isagg)
-            for (i = 0; i < P; ++i) { sc[i] = d; sd[i] = (int64_t)i * d; }
+            for (i = 0; i < P; ++i) { sc[i] = send_len(p, i, d); sd[i] = i; }
     }
 }
 
@@ -396,9 +419,9 @@ static void m_alltoallw(ctx_t *x, int dir)
         a = push(p); a->kind = OP_A2AW; a->coll = coll;
         l.n = 0;
         for (q = 0; q < P; ++q)
-            if (sc[q] > 0) { int id = post_send(p, q, sc[q], (int)(sd[q] / x->d), 0); p->ops[p->nops - 1].coll = coll; il_push(&l, id); }
+            if (sc[q] > 0) { int id = post_send(p, q, sc[q], (int)sd[q], 0); p->ops[p->nops - 1].coll = coll; il_push(&l, id); }
         for (q = 0; q < P; ++q)
-            if (rc[q] > 0) { int id = post_recv(p, q, rc[q], (int)(rd[q] / x->d)); p->ops[p->nops - 1].coll = coll; il_push(&l, id); }
+            if (rc[q] > 0) { int id = post_recv(p, q, rc[q], (int)rd[q]); p->ops[p->nops - 1].coll = coll; il_push(&l, id); }
         wait_list(p, l.v, l.n);
         p->ops[p->nops - 1].coll = coll;
     }
@@ -560,19 +583,19 @@ static void m_pairwise(ctx_t *x, int dir)
             if (pof2) src = dst = x->rank ^ i;
             else { src = (x->rank - i + P) % P; dst = (x->rank + i) % P; }
             if (!fast) {
-                sendrecv(p, dst, sc[dst], sc[dst] ? (int)(sd[dst] / x->d) : -1,
-                         src, rc[src], rc[src] ? (int)(rd[src] / x->d) : -1);
+                sendrecv(p, dst, sc[dst], sc[dst] ? (int)sd[dst] : -1,
+                         src, rc[src], rc[src] ? (int)rd[src] : -1);
                 continue;
             }
             if (!sc[dst] && !rc[src]) continue;
             const int k = m * P + i;
             if (k > 0) sync_step(p, k - 1);
             if (sc[dst] && rc[src]) {
-                sendrecv(p, dst, sc[dst], (int)(sd[dst] / x->d), src, rc[src], (int)(rd[src] / x->d));
+                sendrecv(p, dst, sc[dst], (int)sd[dst], src, rc[src], (int)rd[src]);
             } else if (sc[dst]) {
-                wait1(p, post_send(p, dst, sc[dst], (int)(sd[dst] / x->d), 1));
+                wait1(p, post_send(p, dst, sc[dst], (int)sd[dst], 1));
             } else {
-                wait1(p, post_recv(p, src, rc[src], (int)(rd[src] / x->d)));
+                wait1(p, post_recv(p, src, rc[src], (int)rd[src]));
             }
         }
     }
@@ -614,11 +637,11 @@ static void m13_scattered(ctx_t *x)
             t_mark(p, REG_S);
             for (i = 0; i < ss; ++i) {
                 dst = (x->rank + i + ii) % P;
-                if (rc[dst]) il_push(&l, post_recv(p, dst, rc[dst], (int)(rd[dst] / x->d)));
+                if (rc[dst]) il_push(&l, post_recv(p, dst, rc[dst], (int)rd[dst]));
             }
             for (i = 0; i < ss; ++i) {
                 dst = (x->rank - i - ii + P) % P;
-                if (sc[dst]) il_push(&l, post_send(p, dst, sc[dst], (int)(sd[dst] / x->d), 0));
+                if (sc[dst]) il_push(&l, post_send(p, dst, sc[dst], (int)sd[dst], 0));
             }
             t_delta(p, TG_R, F_POST, REG_S, 0);
             t_acc(p, OP_ACC, TG_G, F_POST, TG_R, F_POST);
@@ -667,11 +690,11 @@ static void m14_scattered(ctx_t *x)
             tstart(p, F_POST);
             for (i = 0; i < ss; ++i) {
                 dst = (x->rank + i + ii) % P;
-                if (rc[dst]) il_push(&l, post_recv(p, dst, rc[dst], (int)(rd[dst] / x->d)));
+                if (rc[dst]) il_push(&l, post_recv(p, dst, rc[dst], (int)rd[dst]));
             }
             for (i = 0; i < ss; ++i) {
                 dst = (x->rank - i - ii + P) % P;
-                if (sc[dst]) il_push(&l, post_send(p, dst, sc[dst], (int)(sd[dst] / x->d), 0));
+                if (sc[dst]) il_push(&l, post_send(p, dst, sc[dst], (int)sd[dst], 0));
             }
             tstop(p, F_POST);
             if (l.n) { tstart(p, F_RECV); wait_list(p, l.v, l.n); tstop(p, F_RECV); }
@@ -787,13 +810,13 @@ static void m19_scattered_isend(ctx_t *x)
             l.n = 0;
             for (i = 0; i < ss; ++i) {
                 dst = (x->rank + i + ii) % P;
-                if (rc[dst]) il_push(&l, post_recv(p, dst, rc[dst], (int)(rd[dst] / x->d)));
+                if (rc[dst]) il_push(&l, post_recv(p, dst, rc[dst], (int)rd[dst]));
             }
             for (i = 0; i < ss; ++i) {
                 dst = (x->rank - i - ii + P) % P;
                 if (sc[dst]) {
                     if (!x->isagg) tstart(p, F_POST);
-                    il_push(&l, post_send_ex(p, dst, sc[dst], (int)(sd[dst] / x->d), 1, 1, 0, -1));
+                    il_push(&l, post_send_ex(p, dst, sc[dst], (int)sd[dst], 1, 1, 0, -1));
                     if (!x->isagg) tstop(p, F_POST);
                 }
             }

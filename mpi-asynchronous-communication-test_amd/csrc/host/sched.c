@@ -130,6 +130,12 @@ static void scratch_layout(xg_sched *s)
     }
 }
 
+/* byte offset of a post's segment (recv = 0) / slot (recv = 1) inside the rank's part */
+static int64_t match_off(const xg_sched *s, int r, int idx, int recv)
+{
+    return s->lens ? (recv ? xg_slot_offset(s, r, idx) : xg_seg_offset(s, r, idx)) : (int64_t)idx * s->d;
+}
+
 static int do_match(xg_sched *s, char *err, size_t errlen)
 {
     int r, i, ns = 0, nr = 0, j;
@@ -148,11 +154,11 @@ static int do_match(xg_sched *s, char *err, size_t errlen)
             const op_t *o = &p->ops[i];
             if (o->kind == OP_SEND) {
                 pst_t t = { o->coll, o->comm, r, o->peer, o->coll >= 0 ? 0 : o->tag, r, o->post, o->idx,
-                            o->cnt * o->esz, o->sb, 0, o->idx >= 0 ? (int64_t)o->idx * s->d : o->off };
+                            o->cnt * o->esz, o->sb, 0, o->idx >= 0 ? match_off(s, r, o->idx, 0) : o->off };
                 S[ns++] = t;
             } else if (o->kind == OP_RECV) {
                 pst_t t = { o->coll, o->comm, o->peer, r, o->coll >= 0 ? 0 : o->tag, r, o->post, o->idx,
-                            o->cnt * o->esz, o->db, 0, o->idx >= 0 ? (int64_t)o->idx * s->d : o->off2 };
+                            o->cnt * o->esz, o->db, 0, o->idx >= 0 ? match_off(s, r, o->idx, 1) : o->off2 };
                 R[nr++] = t;
             }
         }
@@ -198,8 +204,8 @@ static int do_match(xg_sched *s, char *err, size_t errlen)
                 xg_msg *m = new_msg(s);
                 m->src = m->dst = r; m->sseg = o->idx; m->dslot = o->idx2;
                 m->len = o->cnt; m->step = -1; m->flags = XG_MSG_COPY;
-                phys_loc(s, r, o->sb, o->idx >= 0 ? (int64_t)o->idx * s->d : o->off, &m->sbuf, &m->soff);
-                phys_loc(s, r, o->db, o->idx2 >= 0 ? (int64_t)o->idx2 * s->d : o->off2, &m->dbuf, &m->doff);
+                phys_loc(s, r, o->sb, o->idx >= 0 ? match_off(s, r, o->idx, 0) : o->off, &m->sbuf, &m->soff);
+                phys_loc(s, r, o->db, o->idx2 >= 0 ? match_off(s, r, o->idx2, 1) : o->off2, &m->dbuf, &m->doff);
                 p->ops[i].post = s->nmsg - 1;
             }
     }
@@ -330,6 +336,7 @@ void xg_sched_free(xg_sched *s)
     free(s->progs); free(s->msgs); free(s->msg_spost); free(s->msg_rpost); free(s->post_count);
     free(s->barrier_epoch); free(s->scr_base); free(s->scr_size);
     free(s->rank_list); free(s->isagg); free(s->agg_prefix);
+    free(s->lens); free(s->rowpre); free(s->colpre); free(s->myidx);
     free(s);
 }
 
@@ -341,9 +348,56 @@ xg_sched *xg_sched_build(int method, int procs, int cb_nodes, int64_t data_size,
                                barrier_type, eager_limit, 0, err, errlen);
 }
 
+static xg_sched *build(int method, int procs, int cb_nodes, int64_t data_size, const int64_t *lens, int comm_size,
+                       const int *rank_list, int ntimes, int proc_node, int barrier_type,
+                       int64_t eager_limit, int iter, char *err, size_t errlen);
+
 xg_sched *xg_sched_build_iter(int method, int procs, int cb_nodes, int64_t data_size, int comm_size,
                               const int *rank_list, int ntimes, int proc_node, int barrier_type,
                               int64_t eager_limit, int iter, char *err, size_t errlen)
+{
+    return build(method, procs, cb_nodes, data_size, NULL, comm_size, rank_list, ntimes, proc_node, barrier_type,
+                 eager_limit, iter, err, errlen);
+}
+
+xg_sched *xg_sched_build_v(int method, int procs, int cb_nodes, const int64_t *lens, int comm_size,
+                           const int *rank_list, int ntimes, int proc_node, int barrier_type,
+                           int64_t eager_limit, int iter, char *err, size_t errlen)
+{
+    char dummy[8];
+    size_t i, n;
+    int uniform = 1;
+    if (!err) { err = dummy; errlen = sizeof dummy; }
+    err[0] = 0;
+    if (!lens) { snprintf(err, errlen, "no length matrix (lens is NULL)"); return NULL; }
+    if (procs < 1 || cb_nodes < 1 || cb_nodes > procs) {
+        snprintf(err, errlen, "bad sizes P=%d A=%d", procs, cb_nodes);
+        return NULL;
+    }
+    n = (size_t)procs * cb_nodes;
+    for (i = 0; i < n; ++i) {
+        if (lens[i] < 0) {
+            snprintf(err, errlen, "negative length %lld for rank %d, aggregator index %d", (long long)lens[i],
+                     (int)(i / cb_nodes), (int)(i % cb_nodes));
+            return NULL;
+        }
+        uniform &= lens[i] == lens[0];
+    }
+    if (uniform)        /* the old schedule, TAM included */
+        return build(method, procs, cb_nodes, lens[0], NULL, comm_size, rank_list, ntimes, proc_node, barrier_type,
+                     eager_limit, iter, err, errlen);
+    if (method == 15 || method == 16) {
+        snprintf(err, errlen, "method %d (TAM) takes no ragged length matrix: every entry must be equal", method);
+        return NULL;
+    }
+    return build(method, procs, cb_nodes, 0, lens, comm_size, rank_list, ntimes, proc_node, barrier_type,
+                 eager_limit, iter, err, errlen);
+}
+
+/* lens != NULL: a ragged schedule (data_size unused; s->d becomes the longest segment) */
+static xg_sched *build(int method, int procs, int cb_nodes, int64_t data_size, const int64_t *lens, int comm_size,
+                       const int *rank_list, int ntimes, int proc_node, int barrier_type,
+                       int64_t eager_limit, int iter, char *err, size_t errlen)
 {
     xg_sched *s;
     int r, i, *lastidx;
@@ -377,6 +431,29 @@ xg_sched *xg_sched_build_iter(int method, int procs, int cb_nodes, int64_t data_
     lastidx = (int *)xgi_xmalloc(sizeof(int) * procs);
     for (r = 0; r < procs; ++r) lastidx[r] = -1;
     for (i = 0; i < cb_nodes; ++i) lastidx[rank_list[i]] = i;
+    if (lens) {
+        const size_t n = (size_t)procs * cb_nodes;
+        int a;
+        s->lens = (int64_t *)xgi_xmalloc(sizeof(int64_t) * n);
+        memcpy(s->lens, lens, sizeof(int64_t) * n);
+        s->rowpre = (int64_t *)xgi_xmalloc(sizeof(int64_t) * procs * (cb_nodes + 1));
+        s->colpre = (int64_t *)xgi_xmalloc(sizeof(int64_t) * cb_nodes * (procs + 1));
+        s->myidx = (int *)xgi_xmalloc(sizeof(int) * procs);
+        for (r = 0; r < procs; ++r) {
+            int64_t *row = s->rowpre + (size_t)r * (cb_nodes + 1);
+            row[0] = 0;
+            for (a = 0; a < cb_nodes; ++a) {
+                row[a + 1] = row[a] + lens[(size_t)r * cb_nodes + a];
+                if (lens[(size_t)r * cb_nodes + a] > s->d) s->d = lens[(size_t)r * cb_nodes + a];
+            }
+            s->myidx[r] = lastidx[r] >= 0 ? lastidx[r] : 0;
+        }
+        for (a = 0; a < cb_nodes; ++a) {
+            int64_t *col = s->colpre + (size_t)a * (procs + 1);
+            col[0] = 0;
+            for (r = 0; r < procs; ++r) col[r + 1] = col[r] + lens[(size_t)r * cb_nodes + a];
+        }
+    }
     for (r = 0; r < procs; ++r) {
         ctx_t x;
         prog_t *p = &s->progs[r];
@@ -387,6 +464,7 @@ xg_sched *xg_sched_build_iter(int method, int procs, int cb_nodes, int64_t data_
         p->rank = r;
         for (i = 0; i < cb_nodes; ++i)            /* last match, :111-115 / :183-187 */
             if (rank_list[i] == r) x.myindex = i;
+        p->lens = s->lens; p->dir = s->dir; p->A = cb_nodes; p->myindex = x.myindex;
         xgi_program(&x);
     }
     free(lastidx);
@@ -413,6 +491,7 @@ const xg_msg *xg_sched_msgs(const xg_sched *s) { return s->msgs; }
 int xg_sched_nsteps(const xg_sched *s) { return s->nsteps; }
 int xg_sched_direction(const xg_sched *s) { return s->dir; }
 int xg_sched_procs(const xg_sched *s) { return s->P; }
+int xg_sched_ragged(const xg_sched *s) { return s->lens != NULL; }
 
 /* ------------------------------------------------------------------ traces */
 typedef struct { char *buf; size_t len, cap; } sbuf;
@@ -677,12 +756,44 @@ int xgi_nrecv_slots(const xg_sched *s, int r)
     return s->dir == XG_A2M ? (s->isagg[r] ? s->P : 0) : s->A;
 }
 
+/* ragged: is the rank's SEND (recv = 0) / RECV (recv = 1) part an aggregator buffer (P entries,
+ * a column of the matrix) or an every-rank buffer (A entries, a row)? */
+static int agg_side(const xg_sched *s, int recv) { return (s->dir == XG_A2M) == (recv != 0); }
+
+/* ragged: bytes of the rank's SEND / RECV part */
+static int64_t part_bytes(const xg_sched *s, int rank, int recv)
+{
+    if (agg_side(s, recv))
+        return s->isagg[rank] ? s->colpre[(size_t)s->myidx[rank] * (s->P + 1) + s->P] : 0;
+    return s->rowpre[(size_t)rank * (s->A + 1) + s->A];
+}
+
+static int64_t part_offset(const xg_sched *s, int rank, int idx, int recv)
+{
+    int n;
+    if (rank < 0 || rank >= s->P) return -1;
+    n = recv ? xgi_nrecv_slots(s, rank) : xgi_nsend_segs(s, rank);
+    if (idx < 0 || idx > n || !n) return -1;
+    if (!s->lens) return (int64_t)idx * s->d;
+    if (agg_side(s, recv)) return s->colpre[(size_t)s->myidx[rank] * (s->P + 1) + idx];
+    return s->rowpre[(size_t)rank * (s->A + 1) + idx];
+}
+
+int64_t xg_seg_offset(const xg_sched *s, int rank, int seg) { return part_offset(s, rank, seg, 0); }
+int64_t xg_slot_offset(const xg_sched *s, int rank, int slot) { return part_offset(s, rank, slot, 1); }
+
 static int64_t rank_offset(const xg_sched *s, int ngpus, int rank, int recv)
 {
     int lo, hi, g = xg_gpu_of(s->P, ngpus, rank);
     int per_rank = recv ? xgi_nrecv_slots(s, rank) : xgi_nsend_segs(s, rank);
     xg_block_range(s->P, ngpus, g, &lo, &hi);
     if (!per_rank) return -1;
+    if (s->lens) {      /* dense: the parts of the GPU's ranks back to back, rank-major */
+        int64_t o = 0;
+        int q;
+        for (q = lo; q < rank; ++q) o += part_bytes(s, q, recv);
+        return o;
+    }
     /* ranks with a buffer of this kind on the GPU are laid out rank-major */
     if ((s->dir == XG_A2M) == (recv != 0))
         return (int64_t)(s->agg_prefix[rank] - s->agg_prefix[lo]) * s->P * s->d;   /* aggregator buffers */
@@ -707,6 +818,12 @@ int64_t xg_region_bytes(const xg_sched *s, int ngpus, int g, int buf)
     int lo, hi, naggs;
     xg_block_range(s->P, ngpus, g, &lo, &hi);
     naggs = s->agg_prefix[hi] - s->agg_prefix[lo];
+    if (s->lens && (buf == XG_BUF_SEND || buf == XG_BUF_RECV)) {
+        int64_t t = 0;
+        int r;
+        for (r = lo; r < hi; ++r) t += part_bytes(s, r, buf == XG_BUF_RECV);
+        return t;
+    }
     if (buf == XG_BUF_SEND)
         return s->dir == XG_A2M ? (int64_t)(hi - lo) * s->A * s->d : (int64_t)naggs * s->P * s->d;
     if (buf == XG_BUF_RECV)

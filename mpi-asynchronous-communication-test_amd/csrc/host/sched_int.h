@@ -48,6 +48,8 @@ typedef struct {
     int npool, poolcap;
     int nposts, ncoll, nbarrier, rank;
     int64_t hi[NLB];        /* extent of every logical buffer the program touches */
+    const int64_t *lens;    /* ragged schedule: the P x A length matrix (NULL: every segment d bytes) */
+    int dir, A, myindex;    /* what the posts of a ragged schedule read their lengths by */
 } prog_t;
 
 struct xg_sched {
@@ -69,6 +71,11 @@ struct xg_sched {
     int iter;                    /* TAM tags carry +100*iter                        */
     int64_t *scr_base;           /* [rank][NSCR] offset of AGG/SBUF2/RBUF in the rank's scratch */
     int64_t *scr_size;           /* [rank] scratch bytes                            */
+    /* ragged schedule (xg_sched_build_v with lengths that differ; all NULL otherwise) */
+    int64_t *lens;               /* [r * A + a] bytes between rank r and aggregator index a      */
+    int64_t *rowpre;             /* [r * (A + 1) + a] sum of lens[r][< a]                         */
+    int64_t *colpre;             /* [a * (P + 1) + r] sum of lens[< r][a]                         */
+    int *myidx;                  /* [rank] last i with rank_list[i] == rank (0 if none)          */
 };
 
 /* one logical rank's method restatement in progress (programs.c) */

@@ -16,6 +16,9 @@
 //                     out of RCCL staging).  Replaces the shared-memory copies MPI
 //                     does inside Irecv/Issend/Alltoallw.  Misaligned pieces (-d not
 //                     a multiple of 16) are realigned through LDS.
+//  copy_kernel_s      the copy of a ragged exchange: one workgroup per piece at any source
+//                     phase, destination phase and length; aligned 16-B buffer loads of the
+//                     two granules a lane's 16 bytes straddle, funnel shift in registers.
 //  step_engine_kernel a whole GPU-local run of small steps in one persistent
 //                     launch: bursts per step, grid barrier + wall-clock stamp between.
 //  solo_engine_kernel the same for small plans in ONE workgroup: workgroup barrier
@@ -1115,6 +1118,131 @@ __device__ __forceinline__ uint64_t chk_chunk(brsrc rs, int ph, int nfull, int r
         for (int w = 0; w < kThreads / 64; ++w) t += wsum[w];
         atomicAdd(&chk[lo], (unsigned long long)t);
     }
+}
+
+// ---------------------------------------------------------------- shifted piece copy
+// copy_kernel_s<NT>: one workgroup per DCopy piece at ANY source phase, destination phase and
+// length -- the copy of a ragged exchange (xg_sched_build_v), where prefix-sum offsets put almost
+// every segment at an arbitrary byte.  Built as span_chk_kernel reads: no LDS, no barrier.
+//   head  the < 16 bytes that bring the destination to a 16-B boundary, and
+//   tail  the < 16 bytes behind the body: one byte load + byte store per lane (lanes 0.. and 32..);
+//   body  whole 16-B stores at destination-aligned addresses.  Lane j's 16 bytes start at phase
+//         ph = (src + head) & 15 of source granule j: it needs the ALIGNED granules j and j + 1,
+//         both inside a buffer resource that starts at the granule of the body's first source byte
+//         and ends with the granule of the piece's LAST source byte, and funnel-shifts them
+//         (shift_window: v_alignbyte behind uniform selects).  Granule j + 1 is the next lane's j:
+//         in a whole batch of 256 lanes it comes out of that lane's registers (DPP wave shift) and
+//         only lane 63 of a wave loads it; the lanes of a last, partial batch load both (the
+//         second an L1 hit).  Measured: profiles/r08/ragged_copy/summary.txt, run 3 against run 2.
+//         ph == 0 (source and destination agree mod 16): one load per lane, no shift.
+// kShiftU batches of loads (2 kShiftU loads when shifted) are in flight per lane before the first
+// store.  The batches start at the destination's first 128-B line boundary (the up to 7 granules in
+// front of it go one per lane), so a wave's 64 stores fill whole lines.
+// Nothing is written outside [dst, dst + len): every 16-B store is whole and inside the body,
+// chosen by the loop bounds (the destination resource's range, = the body, is never relied on to
+// clip a store), and no granule is read back and merged -- the neighbouring slots are other
+// workgroups'.  Nothing is read outside the 16-B granules of the piece's first and last source byte.
+// A piece too short to have a body (len < head + 16) goes byte by byte.  NT: non-temporal loads and
+// stores.  start: as copy_kernel_g (chains).
+constexpr int kShiftU = 4;
+
+// an offset past the resource of any piece of < kShiftOob bytes (longer ones, which no plan cuts,
+// load both granules): the load returns 0 without an access
+constexpr int kShiftOob = 0x40000000;
+
+// lane l gets lane l + 1's v; lane 63 (no neighbour in the wave) keeps `own`
+__device__ __forceinline__ uint32_t wave_shl1(uint32_t own, uint32_t v)
+{
+    return (uint32_t)__builtin_amdgcn_update_dpp((int)own, (int)v, 0x130, 0xf, 0xf, false);
+}
+
+template <int AUX, bool SHIFT>
+__device__ __forceinline__ void shift_granule(brsrc rs, brsrc rd, int ph, int j)
+{
+    u32x4 a = bload16a<AUX>(rs, j * 16);
+    if constexpr (SHIFT) a = shift_window(a, bload16a<AUX>(rs, j * 16 + 16), ph);
+    bstore16<AUX>(rd, j * 16, a);
+}
+
+// granules [0, nq) of the body; the first `pre` (< 8) of them bring the destination to a 128-B line
+template <int AUX, bool SHIFT>
+__device__ __forceinline__ void shift_body(brsrc rs, brsrc rd, int ph, int nq, int pre)
+{
+    constexpr int U = kShiftU;
+    const int lane = (int)threadIdx.x;
+    if (lane >= 64 && lane - 64 < pre) shift_granule<AUX, SHIFT>(rs, rd, ph, lane - 64);
+    int base = pre;
+    if constexpr (SHIFT) {
+        // whole batches of all 256 lanes (a uniform loop): a lane's second granule is its right
+        // neighbour's first -- taken from that lane's registers (DPP wave shift) instead of loaded
+        // again; only lane 63 of a wave loads it (the others aim past the resource: no access)
+        const int own = (lane & 63) == 63 ? 16 : kShiftOob;
+        for (; nq < (kShiftOob >> 5) && base + U * kThreads <= nq; base += U * kThreads) {
+            u32x4 a[U], b[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                a[u] = bload16a<AUX>(rs, (base + lane + u * kThreads) * 16);
+                b[u] = bload16a<AUX>(rs, (base + lane + u * kThreads) * 16 + own);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                b[u].x = wave_shl1(b[u].x, a[u].x);
+                b[u].y = wave_shl1(b[u].y, a[u].y);
+                b[u].z = wave_shl1(b[u].z, a[u].z);
+                b[u].w = wave_shl1(b[u].w, a[u].w);
+                bstore16<AUX>(rd, (base + lane + u * kThreads) * 16, shift_window(a[u], b[u], ph));
+            }
+        }
+    }
+    int j = base + lane;
+    for (; j + (U - 1) * kThreads < nq; j += U * kThreads) {
+        u32x4 a[U], b[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            a[u] = bload16a<AUX>(rs, (j + u * kThreads) * 16);
+            if constexpr (SHIFT) b[u] = bload16a<AUX>(rs, (j + u * kThreads) * 16 + 16);
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            bstore16<AUX>(rd, (j + u * kThreads) * 16, SHIFT ? shift_window(a[u], b[u], ph) : a[u]);
+    }
+    for (; j < nq; j += kThreads) shift_granule<AUX, SHIFT>(rs, rd, ph, j);
+}
+
+template <bool NT = false>
+__global__ __launch_bounds__(kThreads) void copy_kernel_s(const DCopy *__restrict__ pieces,
+                                                          unsigned long long *start)
+{
+    constexpr int AUX = NT ? kAuxNT : kAuxPlain;
+    if (start && blockIdx.x == 0 && threadIdx.x == 0) *start = (unsigned long long)wall_clock64();
+    const DCopy c = pieces[blockIdx.x];
+    const uint8_t *s = c.src;
+    uint8_t *t = c.dst;
+    const int64_t n = c.len;
+    const int head = (int)((16 - ((uintptr_t)t & 15)) & 15);
+    if (n < head + 16) {
+        bytes_copy(s, t, n);
+        return;
+    }
+    const int64_t body = (n - head) & ~(int64_t)15;
+    const int tail = (int)(n - head - body);
+    const int lane = (int)threadIdx.x;
+    if (lane < head) t[lane] = s[lane];
+    else if (lane >= 32 && lane - 32 < tail) t[head + body + (lane - 32)] = s[head + body + (lane - 32)];
+    const uint8_t *sb = s + head;                    // body source (any phase)
+    const int ph = (int)((uintptr_t)sb & 15);
+    const uint8_t *sa = sb - ph;                     // its granule: >= the granule of the piece's first byte
+    const int64_t recs = (int64_t)((((uintptr_t)s + (uint64_t)n - 1) | 15) + 1 - (uintptr_t)sa);
+    const brsrc rs = make_rsrc(sa, recs);
+    const brsrc rd = make_rsrc(t + head, body);
+    // the first `pre` granules go one per lane (wave 1), so that the batches behind them start on a
+    // 128-B line of the destination: every wave's 1 KiB store then fills 8 whole lines instead of
+    // 7 and two halves it shares with its neighbours
+    const int nq = (int)(body >> 4);
+    const int to_line = (int)((8 - (((uintptr_t)(t + head) >> 4) & 7)) & 7);
+    const int pre = to_line < nq ? to_line : nq;
+    if (ph) shift_body<AUX, true>(rs, rd, ph, nq, pre);
+    else shift_body<AUX, false>(rs, rd, 0, nq, pre);
 }
 
 }  // namespace xgk

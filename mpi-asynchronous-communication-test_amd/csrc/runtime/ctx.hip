@@ -194,6 +194,8 @@ static int init_ctx(xg_ctx *c, const void *uid)
     const char *env = getenv("XG_COPY_VARIANT");          // 0 by size (default), 1 plain, 6 non-temporal
     if (env && (atoi(env) == 1 || atoi(env) == 6)) c->variant = atoi(env);
     else if (env && atoi(env) != 0) fprintf(stderr, "xg: XG_COPY_VARIANT=%s ignored (0, 1 or 6)\n", env);
+    env = getenv("XG_RAGGED_COPY");          // "0": a ragged plan's misaligned launches stay on copy_kernel_g (A/B)
+    c->ragged_copy = !(env && atoi(env) == 0);
     c->engine_max_step = 16 << 20;    // crossover vs one launch per step: profiles/r01_engine_sweep.txt
     env = getenv("XG_ENGINE_MAX_STEP");      // 0: never use the step engine
     if (env) c->engine_max_step = atol(env);

@@ -60,6 +60,9 @@ static int launch_one(xg_plan *p, const CopyLaunch &l, int b, int n, hipStream_t
                        : l.kib == 4 ? xgk::copy_kernel_w<4>
                                     : xgk::copy_kernel_w<xgk::kWaveKiB>;
         hipLaunchKernelGGL(k, dim3(wave_wgs(p, n)), dim3(xgk::kThreads), 0, st, pc, n, start);
+    } else if (l.shift) {
+        const auto k = l.nt ? xgk::copy_kernel_s<true> : xgk::copy_kernel_s<false>;
+        hipLaunchKernelGGL(k, dim3(n), dim3(xgk::kThreads), 0, st, pc, start);
     } else {
         const auto k = l.nt ? xgk::copy_kernel_g<4, true> : xgk::copy_kernel_g<4>;
         hipLaunchKernelGGL(k, dim3(n), dim3(xgk::kThreads), 0, st, pc, start);
@@ -155,6 +158,15 @@ extern "C" int xg_plan_wave_launches(const xg_plan *p, int *grid, int *max_piece
     });
     if (grid) *grid = p->ctx->wave_grid;
     if (max_pieces_per_wave) *max_pieces_per_wave = most;
+    return count;
+}
+
+// The launches of one run (xg_plan_launches' dispatches counted once each) that go to
+// copy_kernel_s, the shifted piece copy.
+extern "C" int xg_plan_shift_launches(const xg_plan *p)
+{
+    int count = 0;
+    each_launch(p, [&](const CopyLaunch &l) { count += l.shift; });
     return count;
 }
 

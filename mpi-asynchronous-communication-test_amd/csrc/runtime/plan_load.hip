@@ -543,6 +543,11 @@ struct TableBuilder {
         const int v = copy_variant(p, l.bytes, reread_run);
         l.nt = v == 6;
         l.stamps = v == 1 || v == 6;
+        // A ragged plan's launch with a piece off the 16-B grid: copy_kernel_s for all its pieces
+        // (region bases are 16-B aligned, xg_regions_adopt insists; every cut below is a multiple
+        // of 16, so a copy's pieces keep its phases).  The cut, the
+        // stream and the stamps stay as they are; a wave launch is aligned and never gets here.
+        l.shift = (dp->flags & XG_DP_RAGGED) && c->ragged_copy && (bits & 15) != 0;
         if (cross && l.bytes >= c->wave_min && l.bytes <= kWaveMax && (bits & 15) == 0 &&
             copy_variant(p, l.bytes, reread_cut) == 1) {
             const int kib = c->wave_kib ? c->wave_kib : wave_kib_for(l.bytes, c->cus);

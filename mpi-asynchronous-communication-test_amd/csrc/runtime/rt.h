@@ -143,6 +143,7 @@ struct xg_ctx {
     int graph;                 // hipGraph replay of multi-launch runs: 1 always, 0 never, -1 latency-bound one-GPU runs
     double wall_hz;            // wall_clock64() rate
     int variant;            // copy kernel variant (copy_variant in plan_load.hip)
+    int ragged_copy;        // 1: a ragged plan's misaligned launches run copy_kernel_s; 0 (XG_RAGGED_COPY=0): copy_kernel_g
     int engine_occ;            // co-resident step-engine workgroups the device admits (plan load caps W)
     // kernel timing session (xg_ktime_begin/end): 1 = an event pair around every
     // copy launch, 2 = one pair around the whole session on the main stream
@@ -169,6 +170,8 @@ struct CopyLaunch {
     int64_t bytes = 0;               // bytes they copy (read + written once)
     int kib = 0;                     // 2 / 4 / 8: copy_kernel_w<kib> over pieces of <= kib KiB; 0: copy_kernel_g<4>
     bool nt = false;                 // copy_kernel_g<4, true>: non-temporal loads and stores
+    bool shift = false;              // copy_kernel_s<nt> for all its pieces: a launch of a ragged plan
+                                     // (XG_DP_RAGGED) with a piece off the 16-B grid (TableBuilder::open)
     bool stamps = false;             // its kernel can stamp its start (a chain step's launch must)
     bool side = false;               // runs on the side stream: fork event before it, join event after it
     bool mark_prev = false;          // holds the previous step's unpacks: that step's mark goes right behind it

@@ -53,7 +53,7 @@ class StepPlan(C.Structure):
 
 
 class DevPlan(C.Structure):
-    _fields_ = [("gpu", C.c_int32), ("ngpus", C.c_int32), ("nsteps", C.c_int32), ("pad", C.c_int32),
+    _fields_ = [("gpu", C.c_int32), ("ngpus", C.c_int32), ("nsteps", C.c_int32), ("flags", C.c_int32),
                 ("region_bytes", C.c_int64 * NBUF), ("ncopy", C.c_int32), ("np2p", C.c_int32),
                 ("copies", C.POINTER(Copy)), ("p2p", C.POINTER(P2P)), ("steps", C.POINTER(StepPlan)),
                 ("local_bytes", C.c_int64), ("remote_send_bytes", C.c_int64),
@@ -116,6 +116,7 @@ BUF_SEND, BUF_RECV, BUF_STAGE_SEND, BUF_STAGE_RECV, BUF_SCRATCH = 0, 1, 2, 3, 4
 PACK_TWO_SIDED, PACK_ONE_SIDED, RELAY, RELAY_COALESCED = 0, 1, 2, 3   # xg_devplan_build_form (xg_sched.h XG_RELAY, XG_RELAY_COALESCED)
 CALL_SEND, CALL_RECV, CALL_BARRIER, CALL_FENCE = 1, 2, 3, 4   # xg_call kinds
 MSG_COPY, MSG_COLL, MSG_CTRL = 1, 2, 4
+DP_RAGGED = 1          # xg_devplan.flags bit 0 (XG_DP_RAGGED)
 TAM_METHODS = (15, 16)
 MPICH_EAGER_LIMIT = 65424
 
@@ -145,7 +146,15 @@ def host():
         h.xg_sched_build_iter.restype = C.c_void_p
         h.xg_sched_build_iter.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int),
                                           C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_char_p, C.c_size_t]
+        h.xg_sched_build_v.restype = C.c_void_p
+        h.xg_sched_build_v.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int, C.POINTER(C.c_int),
+                                       C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_char_p, C.c_size_t]
         h.xg_sched_free.argtypes = [C.c_void_p]
+        h.xg_sched_ragged.argtypes = [C.c_void_p]
+        for fn in ("xg_seg_offset", "xg_slot_offset"):
+            getattr(h, fn).restype = C.c_int64
+            getattr(h, fn).argtypes = [C.c_void_p, C.c_int, C.c_int]
+        h.xg_delivery_lens.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64)]
         for fn in ("xg_sched_nmsg", "xg_sched_nsteps", "xg_sched_direction", "xg_sched_procs"):
             getattr(h, fn).argtypes = [C.c_void_p]
         h.xg_sched_msgs.restype = C.POINTER(Msg)
@@ -323,19 +332,32 @@ class Schedule:
     """One method run (all -k repetitions), compiled to device-wide steps."""
 
     def __init__(self, method, procs, cb_nodes, data_size, comm_size, rank_list, ntimes=1,
-                 eager_limit=MPICH_EAGER_LIMIT, proc_node=1, barrier_type=0, iteration=0):
+                 eager_limit=MPICH_EAGER_LIMIT, proc_node=1, barrier_type=0, iteration=0, lens=None):
+        """lens: a length per (rank, aggregator index) pair, row-major P x A (xg_sched_build_v;
+        data_size is then unused and self.d is the longest segment, or the common one)."""
         h = host()
         self.method, self.P, self.A, self.d, self.c = method, procs, cb_nodes, data_size, comm_size
         self.rank_list = list(rank_list)
         self.ntimes = ntimes
         err = C.create_string_buffer(512)
         rl = (C.c_int * cb_nodes)(*rank_list)
-        self._h = h.xg_sched_build_iter(method, procs, cb_nodes, data_size, comm_size, rl, ntimes,
-                                        proc_node, barrier_type, eager_limit, iteration, err, 512)
+        if lens is not None:
+            flat = [int(x) for x in lens]
+            if len(flat) != procs * cb_nodes:
+                raise XGError("lens must have procs * cb_nodes = %d entries, not %d" % (procs * cb_nodes, len(flat)))
+            self.lens = flat
+            self.d = max(flat) if flat else 0
+            self._h = h.xg_sched_build_v(method, procs, cb_nodes, (C.c_int64 * max(1, len(flat)))(*flat), comm_size,
+                                         rl, ntimes, proc_node, barrier_type, eager_limit, iteration, err, 512)
+        else:
+            self.lens = None
+            self._h = h.xg_sched_build_iter(method, procs, cb_nodes, data_size, comm_size, rl, ntimes,
+                                            proc_node, barrier_type, eager_limit, iteration, err, 512)
         if not self._h:
             raise XGError(err.value.decode())
         self.nsteps = h.xg_sched_nsteps(self._h)
         self.direction = h.xg_sched_direction(self._h)
+        self.ragged = bool(h.xg_sched_ragged(self._h))
 
     def __del__(self):
         if getattr(self, "_h", None) and _host is not None:
@@ -408,6 +430,21 @@ class Schedule:
     def recv_offset(self, ngpus, rank):
         return host().xg_recv_offset(self._h, ngpus, rank)
 
+    def seg_offset(self, rank, seg):
+        """byte offset of segment seg inside the rank's SEND part (xg_seg_offset)"""
+        return host().xg_seg_offset(self._h, rank, seg)
+
+    def slot_offset(self, rank, slot):
+        """byte offset of slot `slot` inside the rank's RECV part (xg_slot_offset)"""
+        return host().xg_slot_offset(self._h, rank, slot)
+
+    def delivery_lens(self, ngpus):
+        """xg_delivery_lens: the length of every delivery, in deliveries() order"""
+        n = host().xg_delivery_lens(self._h, ngpus, None)
+        out = (C.c_int64 * max(1, n))()
+        host().xg_delivery_lens(self._h, ngpus, out)
+        return list(out[:n])
+
     def scratch_offset(self, ngpus, rank):
         return host().xg_scratch_offset(self._h, ngpus, rank)
 
@@ -474,6 +511,7 @@ class DevicePlanView:
             raise XGError("xg_devplan_build_form: out of host memory")
         p = self._p.contents
         self.gpu, self.ngpus, self.nsteps = p.gpu, p.ngpus, p.nsteps
+        self.flags = p.flags
         self.region_bytes = list(p.region_bytes)
         self.copies = [(c.src_buf, c.src_off, c.dst_buf, c.dst_off, c.len) for c in p.copies[:p.ncopy]]
         # (peer, is_send, region, offset, length, group): group 1 = a relay step's second RCCL group
@@ -586,6 +624,8 @@ def device():
         d.xg_run_opts_default.restype = None
         d.xg_exchange.argtypes = [vp, ip, ip, ip, ip, C.POINTER(ip), ip, vp, vp, C.POINTER(Timer), ip, ip,
                                   C.POINTER(RunOpts), C.POINTER(i64), C.c_char_p, C.c_size_t]
+        d.xg_exchange_v.argtypes = [vp, ip, ip, ip, C.POINTER(i64), C.POINTER(ip), ip, vp, vp, C.POINTER(Timer), ip,
+                                    ip, C.POINTER(RunOpts), C.POINTER(i64), C.c_char_p, C.c_size_t]
         d.xg_regions_free.argtypes = [vp]
         d.xg_regions_poison.argtypes = [vp]
         d.xg_regions_ptr.restype = vp
@@ -606,6 +646,7 @@ def device():
         d.xg_plan_launches.argtypes = [vp]
         d.xg_plan_engine_steps.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
         d.xg_plan_wave_launches.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
+        d.xg_plan_shift_launches.argtypes = [vp]
         d.xg_plan_displs.argtypes = [vp, C.POINTER(i64), ip]
         d.xg_ktime_begin.argtypes = [vp, ip, ip]
         d.xg_ktime_end.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(ip), C.POINTER(i64)]
@@ -815,15 +856,16 @@ def payload_check(runs):
     exchange: every receive slot's checksum against its source segment's in the owning run's
     SEND (Schedule.deliveries) -- bytes the library need not know.  Returns the bad (dst, slot)."""
     runs = [runs] if isinstance(runs, MethodRun) else list(runs)
-    G, d = len(runs), runs[0].sched.d
+    G = len(runs)
     dl = runs[0].sched.deliveries(G)
+    ln = runs[0].sched.delivery_lens(G)
     src, dst = [None] * len(dl), [None] * len(dl)
     for g, run in enumerate(runs):
         ks = [k for k, q in enumerate(dl) if q.src_gpu == g]
-        for k, c in zip(ks, chk_spans(run, [(BUF_SEND, dl[k].send_off, d) for k in ks])):
+        for k, c in zip(ks, chk_spans(run, [(BUF_SEND, dl[k].send_off, ln[k]) for k in ks])):
             src[k] = c
         kr = [k for k, q in enumerate(dl) if q.dst_gpu == g]
-        for k, c in zip(kr, chk_spans(run, [(BUF_RECV, dl[k].recv_off, d) for k in kr])):
+        for k, c in zip(kr, chk_spans(run, [(BUF_RECV, dl[k].recv_off, ln[k]) for k in kr])):
             dst[k] = c
     return [(q.dst, q.slot) for k, q in enumerate(dl) if src[k] != dst[k]]
 
@@ -851,6 +893,32 @@ def exchange(ctx, method, procs, cb_nodes, data_size, rank_list, comm_size, send
     return rc, bad.value, list(timers)[:hi.value - lo.value], err.value.decode()
 
 
+def exchange_v(ctx, method, procs, cb_nodes, lens, rank_list, comm_size, send, recv, it=0, ntimes=1,
+               verify=True, proc_node=1, pack_form=-1):
+    """xg_exchange_v: xg_exchange with a length per (rank, aggregator index) pair (lens: row-major
+    P x A) in place of data_size; buffers laid out as a Schedule(..., lens=) says.  Returns what
+    exchange() returns."""
+    d = device()
+    o = RunOpts()
+    d.xg_run_opts_default(C.byref(o))
+    o.verify, o.proc_node = 1 if verify else 0, proc_node
+    if pack_form >= 0:
+        o.pack_form = pack_form
+    lo, hi = C.c_int(), C.c_int()
+    host().xg_block_range(procs, ctx.nranks, ctx.rank, C.byref(lo), C.byref(hi))
+    timers = (Timer * max(1, hi.value - lo.value))()
+    rl = (C.c_int * cb_nodes)(*rank_list)
+    flat = [int(x) for x in lens]
+    if len(flat) != procs * cb_nodes:
+        raise XGError("lens must have procs * cb_nodes = %d entries, not %d" % (procs * cb_nodes, len(flat)))
+    la = (C.c_int64 * max(1, len(flat)))(*flat)
+    bad = C.c_int64()
+    err = C.create_string_buffer(512)
+    rc = d.xg_exchange_v(ctx.handle, method, procs, cb_nodes, la, rl, comm_size, C.c_void_p(send),
+                         C.c_void_p(recv), timers, it, ntimes, C.byref(o), C.byref(bad), err, 512)
+    return rc, bad.value, list(timers)[:hi.value - lo.value], err.value.decode()
+
+
 class MethodRun:
     """prepare_*_data + the compiled plan of one method on this GPU:
     HBM regions, fingerprint fill (untimed), plan upload.  regions: a Regions
@@ -861,6 +929,9 @@ class MethodRun:
     def __init__(self, ctx, sched, it=0, mode=0, pack_max_seg=4 << 20, regions=None, pack_min=0, pack_form=-1,
                  fill=True):
         d = device()
+        if fill and sched.ragged:
+            raise XGError("MethodRun: the fingerprint fill takes no ragged schedule (segments of one length "
+                          "only): pass fill=False, write the payload, and check it with payload_check()")
         self.ctx, self.sched, self.it, self.mode, self.pack_max_seg = ctx, sched, it, mode, pack_max_seg
         self.pack_min, self.pack_form = pack_min, pack_form
         G, g = ctx.nranks, ctx.rank
@@ -925,6 +996,10 @@ class MethodRun:
         """(copy launches that run copy_kernel_w, the context's wave grid, most pieces on one wave)"""
         return plan_wave_launches(self._p)
 
+    def shift_launches(self):
+        """copy launches that run copy_kernel_s, the shifted piece copy (xg_plan_shift_launches)"""
+        return _dev.xg_plan_shift_launches(self._p)
+
     def displs(self):
         """staging displacements of the packed segments, as the device scan computed them"""
         n = _dev.xg_plan_displs(self._p, None, 0)
@@ -961,7 +1036,9 @@ class MethodRun:
     def slot_chk(self):
         """xg_chk64 of every receive slot (self.slots order) by xg_chk_spans -- no fingerprint
         needed; equals verify()[0]"""
-        return chk_spans(self, [(BUF_RECV, off, self.sched.d) for _s, _e, _d, off in self.slots])
+        G, g = self.ctx.nranks, self.ctx.rank
+        ln = [n for q, n in zip(self.sched.deliveries(G), self.sched.delivery_lens(G)) if q.dst_gpu == g]
+        return chk_spans(self, [(BUF_RECV, off, n) for (_s, _e, _d, off), n in zip(self.slots, ln)])
 
     def read(self, buf, off, length):
         out = C.create_string_buffer(max(1, length))
