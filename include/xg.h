@@ -175,6 +175,11 @@ int xg_plan_wave_launches(const xg_plan *p, int *grid, int *max_pieces_per_wave)
  * has XG_DP_RAGGED, every launch with a piece whose source, destination or length is off the 16-B
  * grid (none with XG_RAGGED_COPY=0, and none in any other plan). */
 int xg_plan_shift_launches(const xg_plan *p);
+/* The copy launches that run copy_kernel_x, the extent copy (one workgroup per tile of short
+ * pieces): in a plan whose device plan has XG_DP_EXTENTS (xg_place_plan_build), every launch whose
+ * mean positive copy length is at most the routing threshold (none with XG_EXTENT_COPY=0, and none
+ * in any other plan; such a launch then runs what it would without the flag). */
+int xg_plan_extent_launches(const xg_plan *p);
 /* Staging displacements of the plan's packed segments as computed on the device
  * at load (one wavefront prefix scan per step and direction: the alltoallw
  * translate of mpi_test.c:233-302).  out == NULL: returns their number. */
@@ -289,6 +294,29 @@ int xg_exchange(xg_ctx *ctx, int method, int procs, int cb_nodes, int data_size,
 int xg_exchange_v(xg_ctx *ctx, int method, int procs, int cb_nodes, const int64_t *lens, const int *rank_list,
                   int comm_size, void *send, void *recv, xg_timer *timers, int iter, int ntimes,
                   const xg_run_opts *opts, int64_t *bad_slots, char *err, size_t errlen);
+
+/* xg_exchange_v with the aggregator side PLACED by an offset-length list (exchange_w.c; the list
+ * rules, xg_exts_check and the domain layout: xg_sched.h).  The pair lengths are the sums of the
+ * pairs' extents (xg_exts_lens); the methods are those xg_exchange_v takes for that matrix.
+ *   a2m methods (collective write): send = the dense ragged SEND of xg_exchange_v; recv = this GPU's
+ *     DOMAIN BUFFER (xg_domain_offset / xg_domain_bytes).  The exchange delivers into a dense
+ *     intermediate the library owns, then one GPU-local copy step scatters every extent into the
+ *     domain.  Only the bytes inside extents are written.
+ *   m2a methods (collective read): send = this GPU's domain buffer, recv = the dense ragged RECV.
+ *     The copy step gathers the extents out of the domain first (it is only read), then the
+ *     exchange runs.
+ * The domain buffer obeys xg_regions_adopt's rules (NULL: allocated here).  timers and *bad_slots
+ * mean what they mean in xg_exchange_v; *place_s = the placement step's device time (xg_plan_run).
+ * opts->verify: the exchange's span check runs on the dense side, unchanged, and xg_chk_spans is
+ * taken of every hosted extent on both sides of the placement (one launch per side); *bad_exts
+ * counts the extents that differ.  Every rank must pass the same list and dom_bytes: both are
+ * compared first; a list xg_exts_check refuses (XG_EARG; scatter rules for a2m), or buffers refused
+ * on any rank, fail every rank alike before the exchange's first RCCL call.  Placement posts no
+ * RCCL call.  bad_slots, bad_exts, place_s, timers may be NULL. */
+int xg_exchange_w(xg_ctx *ctx, int method, int procs, int cb_nodes, const xg_ext *exts, int64_t n,
+                  const int64_t *dom_bytes, const int *rank_list, int comm_size, void *send, void *recv,
+                  xg_timer *timers, int iter, int ntimes, const xg_run_opts *opts,
+                  int64_t *bad_slots, int64_t *bad_exts, double *place_s, char *err, size_t errlen);
 
 /* The operators under the reference's names (mpi_test.c line of the original). */
 #define XG_METHOD_DECL(name)                                                                     \

@@ -193,6 +193,8 @@ typedef struct {
 } xg_stepplan;
 
 #define XG_DP_RAGGED 1               /* xg_devplan.flags bit 0: built from a ragged schedule */
+#define XG_DP_EXTENTS 2              /* bit 1: a placement plan (xg_place_plan_build): launches of many
+                                        short copies, which the runtime may run on copy_kernel_x */
 typedef struct {
     int32_t gpu, ngpus, nsteps, flags;
     int64_t region_bytes[XG_NBUF];    /* send, recv, stage_send, stage_recv, scratch  */
@@ -377,6 +379,48 @@ int xg_step_local_meets_unpacks(const xg_devplan *dp, int s);
  * bytes a stage copy writes, or writes bytes one reads -- then the stage copies keep a launch of
  * their own; 0 if all may share one launch; -1 for a bad step (pieces.c). */
 int xg_step_stage_meets_rest(const xg_devplan *dp, int s);
+/* Tiles of one copy_kernel_x dispatch over the ordered pieces of lengths lens[n] (one workgroup per
+ * tile): a tile is a maximal run of consecutive pieces with at most tile_pieces pieces and at most
+ * tile_bytes bytes; a single piece longer than tile_bytes is a tile of its own.  Tile t is pieces
+ * [begin[t], begin[t + 1]).  Returns the tile count (0 for n <= 0; -1 for a cap < 1); begin has
+ * count + 1 entries and may be NULL to query (pieces.c). */
+int xg_extent_tiles(const int64_t *lens, int n, int64_t tile_bytes, int tile_pieces, int32_t *begin);
+
+/* ---------------------------------------------------------------- placement (place.c)
+ * Where the segments of an exchange lie in the aggregators' collective buffers (ROMIO's
+ * others_req[i].offsets / lens): a list of n extents describes the whole job, and every rank
+ * passes the same list.  Extent e: len bytes of pair (rank, aggregator INDEX agg) at byte `off` of
+ * aggregator agg's domain.  The extents of one pair, in list order, carry consecutive bytes of that
+ * pair's segment, so their lengths sum to the pair's length; len == 0 is allowed and ignored; a
+ * pair with no extent has length 0. */
+typedef struct { int32_t rank, agg; int64_t off, len; } xg_ext;
+/* lens[r * cb_nodes + a] (the matrix xg_sched_build_v takes) = sum of the pair's extent lengths.
+ * XG_EARG (xg.h) for a rank or aggregator out of range, a negative length or a sum past int64. */
+int xg_exts_lens(const xg_ext *exts, int64_t n, int procs, int cb_nodes, int64_t *lens);
+/* dom_bytes[a]: the length of aggregator a's domain.  XG_EARG with a reason in err for a rank or
+ * aggregator out of range, a negative off or len, off + len > dom_bytes[agg] (or past int64), a
+ * negative domain length, and -- scatter != 0, the collective write, where two writers to one byte
+ * have no defined result -- two positive extents of one aggregator that overlap (a sort per
+ * aggregator).  A gather (scatter == 0) may read a byte twice.  XG_ENOMEM; XG_OK. */
+int xg_exts_check(const xg_ext *exts, int64_t n, int procs, int cb_nodes, const int64_t *dom_bytes, int scatter,
+                  char *err, size_t errlen);
+/* A GPU's domain buffer: its hosted aggregators' domains back to back, unpadded, in the order
+ * their RECV (a2m) / SEND (m2a) parts have (by aggregator rank).  xg_domain_offset: where
+ * aggregator index a's domain starts in its GPU's buffer (-1: a out of range); xg_domain_bytes:
+ * GPU g's buffer size. */
+int64_t xg_domain_offset(const xg_sched *s, int ngpus, int a, const int64_t *dom_bytes);
+int64_t xg_domain_bytes(const xg_sched *s, int ngpus, int g, const int64_t *dom_bytes);
+/* GPU g's placement plan: one step of pre copies, one per positive extent of the aggregators it
+ * hosts, in list order; no p2p; flags = XG_DP_RAGGED | XG_DP_EXTENTS.  s is the exchange's schedule
+ * (xg_sched_build_v over xg_exts_lens' matrix).  a2m (scatter, after the exchange): region SEND is
+ * the exchange's dense RECV layout -- an extent's source is xg_recv_offset(aggregator rank) +
+ * xg_slot_offset(aggregator rank, rank) + the bytes of the pair's earlier extents -- and region
+ * RECV is the domain buffer.  m2a (gather, before the exchange): SEND is the domain buffer, RECV
+ * the exchange's dense SEND layout (xg_send_offset + xg_seg_offset + ...).  Only those two entries
+ * of region_bytes are set.  The list must have passed xg_exts_check; NULL on out of memory (or a
+ * list that names a rank or aggregator out of range). */
+xg_devplan *xg_place_plan_build(const xg_sched *s, int ngpus, int g, const xg_ext *exts, int64_t n,
+                                const int64_t *dom_bytes);
 
 /* fill: `nsegs` consecutive d-byte segments at `off` in the SEND region,
  * segment i = fingerprint(rank, seed0 + i, iter) (prepare_*_data loops). */

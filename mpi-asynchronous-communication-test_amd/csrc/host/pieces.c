@@ -36,6 +36,34 @@ int64_t xg_piece_size(const int64_t *lens, int n, int64_t chunk, int cus, int64_
     return best_c;
 }
 
+/* The tiles of one copy_kernel_x dispatch: a workgroup there takes a run of short pieces instead
+ * of one piece, so that a 256-B run does not cost a workgroup start.  Greedy in piece order: a
+ * tile closes when the next piece would be its (tile_pieces + 1)-th or would take it past
+ * tile_bytes; a piece longer than tile_bytes stands alone. */
+int xg_extent_tiles(const int64_t *lens, int n, int64_t tile_bytes, int tile_pieces, int32_t *begin)
+{
+    int i, nt = 0, cnt = 0;
+    int64_t bytes = 0;
+    if (tile_bytes < 1 || tile_pieces < 1) return -1;
+    if (!lens || n <= 0) {
+        if (begin) begin[0] = 0;
+        return 0;
+    }
+    for (i = 0; i < n; ++i) {
+        const int64_t l = lens[i] > 0 ? lens[i] : 0;
+        if (cnt && (cnt >= tile_pieces || bytes + l > tile_bytes)) cnt = 0;
+        if (!cnt) {
+            if (begin) begin[nt] = i;
+            ++nt;
+            bytes = 0;
+        }
+        ++cnt;
+        bytes += l;
+    }
+    if (begin) begin[nt] = n;
+    return nt;
+}
+
 /* [off, end) of region buf */
 typedef struct { int64_t lo, hi; } ival;
 

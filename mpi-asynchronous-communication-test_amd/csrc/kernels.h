@@ -19,6 +19,9 @@
 //  copy_kernel_s      the copy of a ragged exchange: one workgroup per piece at any source
 //                     phase, destination phase and length; aligned 16-B buffer loads of the
 //                     two granules a lane's 16 bytes straddle, funnel shift in registers.
+//  copy_kernel_x      the copy of a placement plan's short extents: one workgroup per TILE of up to
+//                     256 pieces; a scan of the pieces' 16-B destination cells, one cell per lane,
+//                     two aligned granules funnel-shifted at a per-lane phase.
 //  step_engine_kernel a whole GPU-local run of small steps in one persistent
 //                     launch: bursts per step, grid barrier + wall-clock stamp between.
 //  solo_engine_kernel the same for small plans in ONE workgroup: workgroup barrier
@@ -1243,6 +1246,134 @@ __global__ __launch_bounds__(kThreads) void copy_kernel_s(const DCopy *__restric
     const int pre = to_line < nq ? to_line : nq;
     if (ph) shift_body<AUX, true>(rs, rd, ph, nq, pre);
     else shift_body<AUX, false>(rs, rd, 0, nq, pre);
+}
+
+// ---------------------------------------------------------------- extent copy
+// copy_kernel_x<NT>: a launch of MANY SHORT pieces (the extents of a placement plan,
+// xg_place_plan_build: runs of 64 B to a few KiB at any byte offset), each at any source phase,
+// destination phase and length.  One workgroup per TILE -- pieces [tile_begin[t], tile_begin[t + 1])
+// of the dispatch, at most kThreads of them and about 32 KiB (xg_extent_tiles) -- instead of one per
+// piece: a 256-B piece is 16 lanes' worth of bytes, and a workgroup start costs as much as 2 KiB of
+// copying (kWgCost).
+//   1. lane i loads piece i's descriptor and counts the 16-B ALIGNED DESTINATION CELLS its piece
+//      touches, ((dst + len - 1) >> 4) - (dst >> 4) + 1;
+//   2. one workgroup-wide exclusive scan of the counts (wave64 shuffle scan, wave totals through
+//      LDS, as displ_scan_kernel) gives every piece its first cell in the tile's cell list; the
+//      descriptors and the scanned counts stay in LDS (6 KiB);
+//   3. the lanes sweep the cells, lane l cell l, l + 256, ...: a binary search over the scanned
+//      counts (8 LDS reads) finds the cell's piece, consecutive lanes get consecutive cells of one
+//      piece (whole 16-B stores side by side).  A cell's 16 source bytes start at any phase of a
+//      granule: the lane loads the two ALIGNED granules they straddle and funnel-shifts them
+//      (shift_window with a per-lane phase: v_alignbyte with a VGPR shift behind per-lane
+//      selects).  kExtU cells' loads (2 kExtU granules) are in flight per lane before the first
+//      store.
+//   4. a cell wholly inside its piece is one aligned 16-B store.  A partial cell -- a piece's head
+//      or tail, or a piece shorter than a cell -- stores exactly the piece's own bytes of it:
+//      whole aligned dwords where all four bytes are the piece's, single bytes otherwise.
+// What it promises (copy_kernel_x):
+//   * nothing outside [dst, dst + len) of any piece is written: every store is chosen by the byte
+//     range [o0, o1) = the piece's bytes of the cell, and no cell is read back and merged -- two
+//     pieces that share a cell each have a cell entry of their own for it and store only their own
+//     bytes, so neighbours (in this tile, another tile or another launch) never disturb each other;
+//   * nothing is read outside the 16-B granules that hold a piece's first and last source byte:
+//     both granule addresses are clamped to [first, last]; a clamped granule only ever supplies
+//     bytes of the window that lie outside the piece, which are never stored;
+//   * no scratch, no atomics, plain vector loads and stores only.
+// A piece of any length up to the launch's piece size is correct (a long one is simply many
+// cells).  NT: non-temporal loads and 16-B stores.  start: as copy_kernel_g (chains).
+constexpr int kExtU = 4;
+typedef __attribute__((address_space(1))) uint8_t g_u8;
+
+// bytes [o0, o1) of the 16-B cell at `cell` from w; o0 == o1: nothing
+template <bool NT>
+__device__ __forceinline__ void ext_store_cell(uint8_t *cell, u32x4 w, int o0, int o1)
+{
+    if (o0 == 0 && o1 == 16) {
+        st16<NT>((g_u4 *)cell, w);
+        return;
+    }
+    const uint32_t d[4] = {w.x, w.y, w.z, w.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        if (o0 <= 4 * q && 4 * q + 4 <= o1) {
+            *(g_u32 *)(cell + 4 * q) = d[q];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (o0 <= 4 * q + j && 4 * q + j < o1) *(g_u8 *)(cell + 4 * q + j) = (uint8_t)(d[q] >> (8 * j));
+        }
+    }
+}
+
+template <bool NT = false>
+__global__ __launch_bounds__(kThreads) void copy_kernel_x(const DCopy *__restrict__ pieces,
+                                                          const int *__restrict__ tile_begin,
+                                                          unsigned long long *start)
+{
+    __shared__ uint64_t l_src[kThreads], l_dst[kThreads];
+    __shared__ int l_len[kThreads], l_cs[kThreads], wsum[kThreads / 64];
+    if (start && blockIdx.x == 0 && threadIdx.x == 0) *start = (unsigned long long)wall_clock64();
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tb = tile_begin[blockIdx.x];
+    const int np = tile_begin[blockIdx.x + 1] - tb;          // 1 .. kThreads (the host's tile cap)
+    uint64_t s = 0, d = 0;
+    int len = 0, x0 = 0;
+    if (tid < np) {
+        const DCopy c = pieces[tb + tid];
+        s = (uint64_t)(uintptr_t)c.src; d = (uint64_t)(uintptr_t)c.dst; len = (int)c.len;
+        if (len > 0) x0 = (int)(((d + (uint64_t)len - 1) >> 4) - (d >> 4)) + 1;
+    }
+    int x = x0;                                             // inclusive scan inside the wave
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) wsum[wave] = x;
+    l_src[tid] = s; l_dst[tid] = d; l_len[tid] = len;
+    __syncthreads();
+    int before = 0, ncell = 0;
+#pragma unroll
+    for (int w = 0; w < kThreads / 64; ++w) {
+        if (w < wave) before += wsum[w];
+        ncell += wsum[w];
+    }
+    l_cs[tid] = before + x - x0;            // piece tid's first cell; == ncell for every lane past the last piece
+    __syncthreads();
+    if (ncell == 0) return;
+    for (int base = 0; base < ncell; base += kExtU * kThreads) {
+        u32x4 a[kExtU], b[kExtU];
+        uint8_t *cell[kExtU];
+        int ph[kExtU], o0[kExtU], o1[kExtU];
+#pragma unroll
+        for (int u = 0; u < kExtU; ++u) {
+            const int c = base + u * kThreads + tid;
+            const bool live = c < ncell;
+            const int cc = live ? c : ncell - 1;            // a lane past the list loads the last cell again, stores nothing
+            int p = 0;                                      // the last piece whose first cell is <= cc
+#pragma unroll
+            for (int step = kThreads / 2; step > 0; step >>= 1)
+                if (l_cs[p + step] <= cc) p += step;
+            const uint64_t D = l_dst[p], S0 = l_src[p];
+            const uint64_t L = (uint64_t)l_len[p];
+            const uint64_t A = (D & ~15ull) + 16ull * (uint64_t)(cc - l_cs[p]);
+            const uint64_t lo = A > D ? A : D, hi = A + 16 < D + L ? A + 16 : D + L;
+            o0[u] = live ? (int)(lo - A) : 0;
+            o1[u] = live ? (int)(hi - A) : 0;
+            cell[u] = (uint8_t *)(uintptr_t)A;
+            // the cell's source window [S, S + 16): S < S0 for a head cell, S + 16 > S0 + L for a tail
+            const uint64_t S = S0 + (A - D);
+            ph[u] = (int)(S & 15);
+            const uint64_t first = S0 & ~15ull, last = (S0 + L - 1) & ~15ull;
+            uint64_t ga = S & ~15ull, gb = ga + (ph[u] ? 16 : 0);
+            ga = ga < first ? first : ga;
+            gb = gb < first ? first : gb > last ? last : gb;
+            a[u] = ld16<NT>((g_cu4 *)(uintptr_t)ga);
+            b[u] = ld16<NT>((g_cu4 *)(uintptr_t)gb);
+        }
+#pragma unroll
+        for (int u = 0; u < kExtU; ++u) ext_store_cell<NT>(cell[u], shift_window(a[u], b[u], ph[u]), o0[u], o1[u]);
+    }
 }
 
 }  // namespace xgk

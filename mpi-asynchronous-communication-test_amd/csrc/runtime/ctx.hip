@@ -196,6 +196,17 @@ static int init_ctx(xg_ctx *c, const void *uid)
     else if (env && atoi(env) != 0) fprintf(stderr, "xg: XG_COPY_VARIANT=%s ignored (0, 1 or 6)\n", env);
     env = getenv("XG_RAGGED_COPY");          // "0": a ragged plan's misaligned launches stay on copy_kernel_g (A/B)
     c->ragged_copy = !(env && atoi(env) == 0);
+    // copy_kernel_x for a placement plan's launches of short extents (TableBuilder::open): "0" keeps
+    // them on copy_kernel_s.  XG_EXTENT_MEAN_MAX / XG_EXTENT_TILE_KIB: the routing threshold and the
+    // tile's byte cap, for the A/B of profiles/extent_copy_ab.py
+    env = getenv("XG_EXTENT_COPY");
+    c->extent_copy = env ? atoi(env) != 0 : kExtDefault;
+    c->extent_mean_max = kExtMeanMax;
+    env = getenv("XG_EXTENT_MEAN_MAX");
+    if (env && atol(env) > 0) c->extent_mean_max = atol(env);
+    c->extent_tile = kExtTileBytes;
+    env = getenv("XG_EXTENT_TILE_KIB");
+    if (env && atoi(env) > 0 && atoi(env) <= 1024) c->extent_tile = (int64_t)atoi(env) << 10;
     c->engine_max_step = 16 << 20;    // crossover vs one launch per step: profiles/r01_engine_sweep.txt
     env = getenv("XG_ENGINE_MAX_STEP");      // 0: never use the step engine
     if (env) c->engine_max_step = atol(env);

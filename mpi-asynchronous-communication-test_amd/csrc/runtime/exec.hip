@@ -60,6 +60,13 @@ static int launch_one(xg_plan *p, const CopyLaunch &l, int b, int n, hipStream_t
                        : l.kib == 4 ? xgk::copy_kernel_w<4>
                                     : xgk::copy_kernel_w<xgk::kWaveKiB>;
         hipLaunchKernelGGL(k, dim3(wave_wgs(p, n)), dim3(xgk::kThreads), 0, st, pc, n, start);
+    } else if (l.ext) {
+        // one workgroup per tile of the dispatch (which one: by its first piece)
+        int k = 0;
+        while (k + 1 < l.ndisp && p->cuts[l.cut + k + 1] <= b) ++k;
+        const auto kx = l.nt ? xgk::copy_kernel_x<true> : xgk::copy_kernel_x<false>;
+        hipLaunchKernelGGL(kx, dim3(p->xt_n[l.xt + k]), dim3(xgk::kThreads), 0, st, pc, p->d_xt + p->xt_off[l.xt + k],
+                           start);
     } else if (l.shift) {
         const auto k = l.nt ? xgk::copy_kernel_s<true> : xgk::copy_kernel_s<false>;
         hipLaunchKernelGGL(k, dim3(n), dim3(xgk::kThreads), 0, st, pc, start);
@@ -167,6 +174,14 @@ extern "C" int xg_plan_shift_launches(const xg_plan *p)
 {
     int count = 0;
     each_launch(p, [&](const CopyLaunch &l) { count += l.shift; });
+    return count;
+}
+
+// ... and those that go to copy_kernel_x, the extent copy of placement plans.
+extern "C" int xg_plan_extent_launches(const xg_plan *p)
+{
+    int count = 0;
+    each_launch(p, [&](const CopyLaunch &l) { count += l.ext; });
     return count;
 }
 

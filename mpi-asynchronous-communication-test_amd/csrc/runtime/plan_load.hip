@@ -548,7 +548,15 @@ struct TableBuilder {
         // of 16, so a copy's pieces keep its phases).  The cut, the
         // stream and the stamps stay as they are; a wave launch is aligned and never gets here.
         l.shift = (dp->flags & XG_DP_RAGGED) && c->ragged_copy && (bits & 15) != 0;
-        if (cross && l.bytes >= c->wave_min && l.bytes <= kWaveMax && (bits & 15) == 0 &&
+        // A placement plan's launch of short copies (mean positive length <= extent_mean_max):
+        // copy_kernel_x, one workgroup per TILE of pieces (tile_launches, after the pieces are
+        // ordered and the dispatches cut).  The cut, the ordering, the stream and the stamps stay.
+        int64_t npos = 0;
+        for (int64_t n : lens) npos += n > 0;
+        l.ext = (dp->flags & XG_DP_EXTENTS) && c->extent_copy && l.stamps && c->chunk <= (1 << 24) &&
+                l.bytes <= npos * c->extent_mean_max;
+        if (l.ext) l.shift = false;
+        if (!l.ext && cross && l.bytes >= c->wave_min && l.bytes <= kWaveMax && (bits & 15) == 0 &&
             copy_variant(p, l.bytes, reread_cut) == 1) {
             const int kib = c->wave_kib ? c->wave_kib : wave_kib_for(l.bytes, c->cus);
             chunk = (int64_t)kib << 10;
@@ -771,6 +779,31 @@ static void cut_launches(xg_plan *p)
     }
 }
 
+// The tile table of every dispatch of every copy_kernel_x launch: xg_extent_tiles (libxghost) over the
+// dispatch's pieces as they are ordered and cut, so a dispatch's tiles cover exactly its pieces.
+static bool tile_launches(xg_plan *p)
+{
+    const xg_ctx *c = p->ctx;
+    std::vector<int64_t> lens;
+    std::vector<int32_t> begin;
+    for (CopyLaunch &l : p->launches) {
+        if (!l.ext) continue;
+        l.xt = (int)p->xt_off.size();
+        for (int k = 0; k < l.ndisp; ++k) {
+            const int b = p->cuts[l.cut + k], n = p->cuts[l.cut + k + 1] - b;
+            lens.resize(n);
+            for (int i = 0; i < n; ++i) lens[i] = p->plen[b + i + 1] - p->plen[b + i];
+            begin.resize((size_t)n + 1);
+            const int nt = xg_extent_tiles(lens.data(), n, c->extent_tile, kExtTilePieces, begin.data());
+            if (nt < 0 || (n > 0 && (nt == 0 || begin[0] != 0 || begin[nt] != n))) return false;
+            p->xt_off.push_back((int)p->xt_begin.size());
+            p->xt_n.push_back(nt);
+            p->xt_begin.insert(p->xt_begin.end(), begin.begin(), begin.begin() + nt + 1);
+        }
+    }
+    return true;
+}
+
 // Chains (xg_plan::chain_end).  A chain step: no engine segment's, no RCCL, no unpack, no
 // barrier, and every launch of it on the main stream with a kernel that can stamp its start.
 static bool find_chains(xg_plan *p)
@@ -808,6 +841,10 @@ static int plan_upload(xg_plan *p, const std::vector<xgk::DCopy> &pieces, DisplS
     if (p->npieces) {
         HIPCHK(hipMalloc(&p->d_pieces, sizeof(xgk::DCopy) * pieces.size()));
         HIPCHK(hipMemcpy(p->d_pieces, pieces.data(), sizeof(xgk::DCopy) * pieces.size(), hipMemcpyHostToDevice));
+    }
+    if (!p->xt_begin.empty()) {
+        HIPCHK(hipMalloc(&p->d_xt, sizeof(int) * p->xt_begin.size()));
+        HIPCHK(hipMemcpy(p->d_xt, p->xt_begin.data(), sizeof(int) * p->xt_begin.size(), hipMemcpyHostToDevice));
     }
     p->need_mark.assign(p->nsteps, 1);
     p->fork.assign(p->nsteps, nullptr);
@@ -854,6 +891,11 @@ extern "C" int xg_plan_load(xg_ctx *c, xg_regions *r, const xg_devplan *dp, xg_p
     p->plen.assign(pieces.size() + 1, 0);
     for (size_t i = 0; i < pieces.size(); ++i) p->plen[i + 1] = p->plen[i] + pieces[i].len;
     cut_launches(p);
+    if (!tile_launches(p)) {
+        fprintf(stderr, "xg_plan_load: the tiles of a copy_kernel_x dispatch do not cover its pieces\n");
+        delete p;
+        return XG_EARG;
+    }
     if (const int rc = plan_upload(p, pieces, ds)) {
         xg_plan_free(p);        // frees whatever the upload got to
         return rc;
@@ -883,7 +925,7 @@ extern "C" int xg_plan_free(xg_plan *p)
     keep(hipStreamSynchronize(p->ctx->stream));
     keep(hipStreamSynchronize(p->ctx->side));
     for (void *q : {(void *)p->d_pieces, (void *)p->d_sb, (void *)p->d_epieces, (void *)p->d_engine,
-                    (void *)p->d_disp, (void *)p->d_solo, (void *)p->d_cstamp, (void *)p->d_gstamp})
+                    (void *)p->d_disp, (void *)p->d_solo, (void *)p->d_cstamp, (void *)p->d_gstamp, (void *)p->d_xt})
         if (q) keep(hipFree(q));
     if (p->db) keep(hipHostFree((void *)p->db));
     for (auto &e : p->fork) if (e) keep(hipEventDestroy(e));

@@ -144,6 +144,9 @@ struct xg_ctx {
     double wall_hz;            // wall_clock64() rate
     int variant;            // copy kernel variant (copy_variant in plan_load.hip)
     int ragged_copy;        // 1: a ragged plan's misaligned launches run copy_kernel_s; 0 (XG_RAGGED_COPY=0): copy_kernel_g
+    int extent_copy;        // 1: a placement plan's (XG_DP_EXTENTS) launches of short copies run copy_kernel_x
+    int64_t extent_mean_max;   // ... when the launch's mean positive copy length is <= this (kExtMeanMax)
+    int64_t extent_tile;       // bytes per copy_kernel_x tile (kExtTileBytes)
     int engine_occ;            // co-resident step-engine workgroups the device admits (plan load caps W)
     // kernel timing session (xg_ktime_begin/end): 1 = an event pair around every
     // copy launch, 2 = one pair around the whole session on the main stream
@@ -172,6 +175,10 @@ struct CopyLaunch {
     bool nt = false;                 // copy_kernel_g<4, true>: non-temporal loads and stores
     bool shift = false;              // copy_kernel_s<nt> for all its pieces: a launch of a ragged plan
                                      // (XG_DP_RAGGED) with a piece off the 16-B grid (TableBuilder::open)
+    bool ext = false;                // copy_kernel_x<nt>: a launch of short copies of a placement plan
+                                     // (XG_DP_EXTENTS; TableBuilder::open), one workgroup per TILE of pieces:
+                                     // dispatch k's tiles are xg_plan::xt_begin[xt_off[xt + k] ..], xt_n[xt + k] of them
+    int xt = 0;
     bool stamps = false;             // its kernel can stamp its start (a chain step's launch must)
     bool side = false;               // runs on the side stream: fork event before it, join event after it
     bool mark_prev = false;          // holds the previous step's unpacks: that step's mark goes right behind it
@@ -241,6 +248,11 @@ struct xg_plan {
     std::vector<int32_t> call_begin;        // nsteps + 1: where each step's calls start
     std::vector<CopyLaunch> launches;       // every step's copy launches (StepR::l_b .. l_e), fixed at load
     std::vector<int> cuts;                  // their dispatches' piece boundaries (CopyLaunch::cut)
+    // copy_kernel_x tile tables, one per dispatch of every `ext` launch (xg_extent_tiles over the
+    // dispatch's ordered pieces): xt_n[i] tiles, tile t = pieces [xt_begin[xt_off[i] + t], .. + t + 1])
+    // of the dispatch (indices relative to its first piece); d_xt: xt_begin on the device
+    std::vector<int> xt_begin, xt_off, xt_n;
+    int *d_xt = nullptr;
     std::vector<hipEvent_t> fork, join;     // per step with a side-stream launch: main -> side, side -> main
     int variant = 0;
     bool streaming = false;                 // one run copies more than the Infinity Cache holds (read + write)
@@ -334,6 +346,13 @@ constexpr int64_t kNtMin = 128 << 20;      // launches of >= this many bytes str
 constexpr int64_t kNtStream = 4 << 20;     // ... and, in a streaming plan, launches of >= this many
 constexpr int64_t kGridCacheMax = 256 << 20;   // grid_pays: a run of <= this many bytes stays in the MALL
 constexpr int64_t kWgCost = 2048;          // a copy workgroup's fixed start, bytes-equivalent (xg_piece_size)
+// copy_kernel_x (placement plans): tile caps (a workgroup takes at most kExtTilePieces pieces --
+// one descriptor per lane -- and about kExtTileBytes bytes), the mean copy length up to which a
+// launch runs it, and whether it runs at all without XG_EXTENT_COPY (copy_kernel_x)
+constexpr int64_t kExtTileBytes = 32 << 10;
+constexpr int kExtTilePieces = xgk::kThreads;
+constexpr int64_t kExtMeanMax = 1024;
+constexpr int kExtDefault = 1;
 constexpr int64_t kWaveMax = 32 << 20;     // copy_kernel_w up to this launch size (profiles/r03/wave_local/)
 // Piece KiB of a copy_kernel_w launch of `bytes`: the largest of 8 / 4 / 2 that still gives every
 // CU a 4-wave workgroup (bytes / piece >= 4 x CUs): a 4 MiB launch in 8 KiB pieces is 512 waves =

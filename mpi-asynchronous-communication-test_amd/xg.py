@@ -104,6 +104,11 @@ class BufSpan(C.Structure):
     _fields_ = [("buf", C.c_int32), ("pad", C.c_int32), ("off", C.c_int64), ("len", C.c_int64)]
 
 
+class Ext(C.Structure):
+    """xg_ext: len bytes of pair (rank, aggregator index agg) at byte off of aggregator agg's domain"""
+    _fields_ = [("rank", C.c_int32), ("agg", C.c_int32), ("off", C.c_int64), ("len", C.c_int64)]
+
+
 class RunOpts(C.Structure):
     """xg_run_opts"""
     _fields_ = [("verify", C.c_int), ("fingerprint", C.c_int), ("eager_limit", C.c_int64),
@@ -117,6 +122,8 @@ PACK_TWO_SIDED, PACK_ONE_SIDED, RELAY, RELAY_COALESCED = 0, 1, 2, 3   # xg_devpl
 CALL_SEND, CALL_RECV, CALL_BARRIER, CALL_FENCE = 1, 2, 3, 4   # xg_call kinds
 MSG_COPY, MSG_COLL, MSG_CTRL = 1, 2, 4
 DP_RAGGED = 1          # xg_devplan.flags bit 0 (XG_DP_RAGGED)
+DP_EXTENTS = 2         # bit 1 (XG_DP_EXTENTS): a placement plan, short launches may run copy_kernel_x
+EARG, ENOMEM = 3, 4    # XG_EARG, XG_ENOMEM
 TAM_METHODS = (15, 16)
 MPICH_EAGER_LIMIT = 65424
 
@@ -195,6 +202,16 @@ def host():
         h.xg_step_stage_meets_rest.argtypes = [C.POINTER(DevPlan), C.c_int]
         h.xg_piece_size.restype = C.c_int64
         h.xg_piece_size.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_int, C.c_int64]
+        h.xg_extent_tiles.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int32)]
+        h.xg_exts_lens.argtypes = [C.POINTER(Ext), C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        h.xg_exts_check.argtypes = [C.POINTER(Ext), C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int,
+                                    C.c_char_p, C.c_size_t]
+        h.xg_domain_offset.restype = C.c_int64
+        h.xg_domain_offset.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        h.xg_domain_bytes.restype = C.c_int64
+        h.xg_domain_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        h.xg_place_plan_build.restype = C.POINTER(DevPlan)
+        h.xg_place_plan_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Ext), C.c_int64, C.POINTER(C.c_int64)]
         h.xg_fill_runs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SegRun)]
         h.xg_verify_slots.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Slot)]
         h.xg_deliveries.argtypes = [C.c_void_p, C.c_int, C.POINTER(Delivery)]
@@ -321,6 +338,44 @@ def piece_size(lens, chunk=32768, cus=256, wg_cost=2048):
     """xg_piece_size: the workgroup piece size of one copy launch over copies of these lengths"""
     arr = (C.c_int64 * max(1, len(lens)))(*lens)
     return host().xg_piece_size(arr, len(lens), chunk, cus, wg_cost)
+
+
+def extent_tiles(lens, tile_bytes=32768, tile_pieces=256):
+    """xg_extent_tiles: the tiles of one copy_kernel_x dispatch over pieces of these lengths, as the
+    list of tile boundaries (count + 1 entries); None for a cap < 1"""
+    n = len(lens)
+    arr = (C.c_int64 * max(1, n))(*lens)
+    nt = host().xg_extent_tiles(arr, n, tile_bytes, tile_pieces, None)
+    if nt < 0:
+        return None
+    begin = (C.c_int32 * (nt + 1))()
+    assert host().xg_extent_tiles(arr, n, tile_bytes, tile_pieces, begin) == nt
+    return list(begin)
+
+
+def _ext_array(exts):
+    """exts: Ext records or (rank, agg, off, len) tuples -> (C array, n)"""
+    v = [e if isinstance(e, Ext) else Ext(*[int(x) for x in e]) for e in exts]
+    return (Ext * max(1, len(v)))(*v), len(v)
+
+
+def exts_lens(exts, procs, cb_nodes):
+    """xg_exts_lens: the P x A length matrix (row-major) of an extent list; XGError when refused"""
+    arr, n = _ext_array(exts)
+    out = (C.c_int64 * (procs * cb_nodes))()
+    if host().xg_exts_lens(arr, n, procs, cb_nodes, out) != 0:
+        raise XGError("xg_exts_lens: rank or aggregator out of range, negative length or overflow")
+    return list(out)
+
+
+def exts_check(exts, procs, cb_nodes, dom_bytes, scatter=True):
+    """xg_exts_check -> (code, reason): (0, "") for a list that may be placed (scatter: as a
+    collective write, where extents of one aggregator may not overlap)"""
+    arr, n = _ext_array(exts)
+    dom = (C.c_int64 * max(1, cb_nodes))(*[int(x) for x in dom_bytes])
+    err = C.create_string_buffer(512)
+    rc = host().xg_exts_check(arr, n, procs, cb_nodes, dom, 1 if scatter else 0, err, 512)
+    return rc, err.value.decode()
 
 
 def method_label(method):
@@ -454,6 +509,26 @@ class Schedule:
     def devplan(self, ngpus, g, pack_max_seg=4 << 20, pack_min=0, pack_form=-1):
         return DevicePlanView(self, ngpus, g, pack_max_seg, pack_min, pack_form)
 
+    def place_plan(self, ngpus, g, exts, dom_bytes):
+        """xg_place_plan_build: GPU g's placement plan of this (exchange) schedule for an extent
+        list, as a DevicePlanView (one step, one copy per hosted positive extent, in list order)"""
+        arr, n = _ext_array(exts)
+        dom = (C.c_int64 * max(1, self.A))(*[int(x) for x in dom_bytes])
+        p = host().xg_place_plan_build(self._h, ngpus, g, arr, n, dom)
+        if not p:
+            raise XGError("xg_place_plan_build: out of host memory, or a rank / aggregator out of range")
+        return DevicePlanView(self, ngpus, g, 0, plan=p)
+
+    def domain_offset(self, ngpus, a, dom_bytes):
+        """xg_domain_offset: where aggregator index a's domain starts in its GPU's domain buffer"""
+        dom = (C.c_int64 * max(1, self.A))(*[int(x) for x in dom_bytes])
+        return host().xg_domain_offset(self._h, ngpus, a, dom)
+
+    def domain_bytes(self, ngpus, g, dom_bytes):
+        """xg_domain_bytes: the size of GPU g's domain buffer"""
+        dom = (C.c_int64 * max(1, self.A))(*[int(x) for x in dom_bytes])
+        return host().xg_domain_bytes(self._h, ngpus, g, dom)
+
     def check_pairing(self, ngpus, pack_max_seg=4 << 20, pack_min=0, pack_form=-1, self_max=0):
         """Refuse (XGError) a job whose GPUs' RCCL calls RCCL would not pair step by step
         (xg_devplans_match over every GPU's plan, built in C, the calls listed with the
@@ -501,11 +576,11 @@ class Schedule:
 class DevicePlanView:
     """Python view of xg_devplan (host memory), used by the CPU plan tests."""
 
-    def __init__(self, sched, ngpus, g, pack_max_seg, pack_min=0, pack_form=-1):
+    def __init__(self, sched, ngpus, g, pack_max_seg, pack_min=0, pack_form=-1, plan=None):
         self.sched = sched
         # pack_form: PACK_TWO_SIDED, PACK_ONE_SIDED, RELAY, RELAY_COALESCED, or -1 = the library's
-        # default (xg_sched.h)
-        self._p = host().xg_devplan_build_form(sched.handle, ngpus, g, pack_max_seg, pack_min, pack_form)
+        # default (xg_sched.h); plan: a built xg_devplan to view and own (Schedule.place_plan)
+        self._p = plan or host().xg_devplan_build_form(sched.handle, ngpus, g, pack_max_seg, pack_min, pack_form)
         if not self._p:
             self._p = None
             raise XGError("xg_devplan_build_form: out of host memory")
@@ -647,6 +722,10 @@ def device():
         d.xg_plan_engine_steps.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
         d.xg_plan_wave_launches.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
         d.xg_plan_shift_launches.argtypes = [vp]
+        d.xg_plan_extent_launches.argtypes = [vp]
+        d.xg_exchange_w.argtypes = [vp, ip, ip, ip, C.POINTER(Ext), i64, C.POINTER(i64), C.POINTER(ip), ip, vp, vp,
+                                    C.POINTER(Timer), ip, ip, C.POINTER(RunOpts), C.POINTER(i64), C.POINTER(i64),
+                                    C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
         d.xg_plan_displs.argtypes = [vp, C.POINTER(i64), ip]
         d.xg_ktime_begin.argtypes = [vp, ip, ip]
         d.xg_ktime_end.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(ip), C.POINTER(i64)]
@@ -919,6 +998,85 @@ def exchange_v(ctx, method, procs, cb_nodes, lens, rank_list, comm_size, send, r
     return rc, bad.value, list(timers)[:hi.value - lo.value], err.value.decode()
 
 
+def exchange_w(ctx, method, procs, cb_nodes, exts, dom_bytes, rank_list, comm_size, send, recv, it=0, ntimes=1,
+               verify=True, proc_node=1, pack_form=-1):
+    """xg_exchange_w: xg_exchange_v with the aggregator side placed by the extent list (a2m: send =
+    dense ragged SEND, recv = this GPU's domain buffer; m2a: send = the domain buffer, recv = dense
+    ragged RECV; addresses as int).  Returns (rc, bad_slots, bad_exts, place_s, [Timer of every
+    hosted rank], error text); raises nothing, so that every rank of a job sees the code."""
+    d = device()
+    o = RunOpts()
+    d.xg_run_opts_default(C.byref(o))
+    o.verify, o.proc_node = 1 if verify else 0, proc_node
+    if pack_form >= 0:
+        o.pack_form = pack_form
+    lo, hi = C.c_int(), C.c_int()
+    host().xg_block_range(procs, ctx.nranks, ctx.rank, C.byref(lo), C.byref(hi))
+    timers = (Timer * max(1, hi.value - lo.value))()
+    rl = (C.c_int * cb_nodes)(*rank_list)
+    arr, n = _ext_array(exts)
+    dom = (C.c_int64 * max(1, cb_nodes))(*[int(x) for x in dom_bytes])
+    bad, bad_e, place_s = C.c_int64(), C.c_int64(), C.c_double()
+    err = C.create_string_buffer(512)
+    rc = d.xg_exchange_w(ctx.handle, method, procs, cb_nodes, arr, n, dom, rl, comm_size, C.c_void_p(send),
+                         C.c_void_p(recv), timers, it, ntimes, C.byref(o), C.byref(bad), C.byref(bad_e),
+                         C.byref(place_s), err, 512)
+    return rc, bad.value, bad_e.value, place_s.value, list(timers)[:hi.value - lo.value], err.value.decode()
+
+
+class PlaceRun:
+    """One GPU's placement step on its own: the placement plan of a schedule and an extent list
+    (Schedule.place_plan) loaded over regions whose SEND / RECV are the caller's (addresses as int)
+    or allocated here.  a2m: SEND = the dense RECV layout of the exchange, RECV = the domain
+    buffer; m2a: SEND = the domain buffer, RECV = the dense SEND layout."""
+
+    def __init__(self, ctx, sched, exts, dom_bytes, send=None, recv=None):
+        d = device()
+        self.ctx, self.sched = ctx, sched
+        self.view = sched.place_plan(ctx.nranks, ctx.rank, exts, dom_bytes)
+        # the list index of every hosted positive extent, in the plan's copy order
+        self.ext_index = [i for i, e in enumerate(_ext_array(exts)[0][:len(exts)])
+                          if e.len > 0 and sched.gpu_of(ctx.nranks, sched.rank_list[e.agg]) == ctx.rank]
+        self.regions = Regions.adopt(ctx, self.view.region_bytes, send=send, recv=recv)
+        self._r = self.regions._r
+        self._p = C.c_void_p()
+        _check(d.xg_plan_load(ctx.handle, self._r, self.view.ptr, C.byref(self._p)), "xg_plan_load")
+
+    def run(self):
+        """one timed run -> the placement step's device seconds"""
+        done, post, wall = (C.c_double * 1)(), (C.c_double * 1)(), C.c_double()
+        _check(_dev.xg_plan_run(self._p, done, post, C.byref(wall)), "xg_plan_run")
+        return done[0]
+
+    def extent_launches(self):
+        """copy launches that run copy_kernel_x (xg_plan_extent_launches)"""
+        return _dev.xg_plan_extent_launches(self._p)
+
+    def shift_launches(self):
+        return _dev.xg_plan_shift_launches(self._p)
+
+    @property
+    def launches(self):
+        return _dev.xg_plan_launches(self._p)
+
+    def close(self):
+        if getattr(self, "_p", None):
+            _check(_dev.xg_plan_free(self._p), "xg_plan_free")
+            self._p = None
+        if getattr(self, "regions", None):
+            self.regions.close()
+            self.regions = None
+
+
+def place_check(run):
+    """A PlaceRun after its run: xg_chk_spans of every hosted extent on both sides of the placement
+    (one launch per side).  Returns the list indices of the extents whose sides differ."""
+    cp = run.view.copies
+    src = chk_spans(run, [(sb, so, n) for (sb, so, _db, _do, n) in cp])
+    dst = chk_spans(run, [(db, do, n) for (_sb, _so, db, do, n) in cp])
+    return [run.ext_index[k] for k in range(len(cp)) if src[k] != dst[k]]
+
+
 class MethodRun:
     """prepare_*_data + the compiled plan of one method on this GPU:
     HBM regions, fingerprint fill (untimed), plan upload.  regions: a Regions
@@ -999,6 +1157,10 @@ class MethodRun:
     def shift_launches(self):
         """copy launches that run copy_kernel_s, the shifted piece copy (xg_plan_shift_launches)"""
         return _dev.xg_plan_shift_launches(self._p)
+
+    def extent_launches(self):
+        """copy launches that run copy_kernel_x, the extent copy (xg_plan_extent_launches)"""
+        return _dev.xg_plan_extent_launches(self._p)
 
     def displs(self):
         """staging displacements of the packed segments, as the device scan computed them"""
