@@ -180,6 +180,11 @@ int xg_plan_shift_launches(const xg_plan *p);
  * mean positive copy length is at most the routing threshold (none with XG_EXTENT_COPY=0, and none
  * in any other plan; such a launch then runs what it would without the flag). */
 int xg_plan_extent_launches(const xg_plan *p);
+/* The copy launches that run copy_kernel_q, the small-piece copy: a step's local launch that is
+ * uniform (every positive copy the same length), 16-B aligned, without packs, would run
+ * copy_kernel_g<4> and moves at least 112 MiB (XG_SMALL_PIECE_MIN, a test hook, lowers that; none
+ * with XG_SMALL_PIECES=0).  *kib (may be NULL): their piece size, 4 or 8, or 0 when there is none. */
+int xg_plan_small_launches(const xg_plan *p, int *kib);
 /* Staging displacements of the plan's packed segments as computed on the device
  * at load (one wavefront prefix scan per step and direction: the alltoallw
  * translate of mpi_test.c:233-302).  out == NULL: returns their number. */

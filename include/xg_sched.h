@@ -386,6 +386,40 @@ int xg_step_stage_meets_rest(const xg_devplan *dp, int s);
  * count + 1 entries and may be NULL to query (pieces.c). */
 int xg_extent_tiles(const int64_t *lens, int n, int64_t tile_bytes, int tile_pieces, int32_t *begin);
 
+/* Small-piece launches (copy_kernel_q, kernels.h): a UNIFORM launch -- `copies` copies of `len`
+ * bytes each, listed one table row per copy -- in pieces of `piece` bytes, one workgroup per piece,
+ * with no per-piece table: workgroup b finds its piece by arithmetic.  ppc = ceil(len / piece)
+ * pieces per copy, copies * ppc workgroups in all (< 2^31: the callers check).  The copies are
+ * taken in groups of k consecutive rows (the last group may be shorter): inside a group the
+ * workgroups go round the group's copies piece by piece -- workgroup r of a group of kk copies
+ * serves the group's copy r % kk, piece r / kk -- so k = 1 is plain row order.  A copy's last
+ * piece holds the rest of it (n <= piece).  The same function runs in the kernel (every operand
+ * is workgroup-uniform) and on the host (dispatch byte counts, tests); libxghost exports both
+ * (pieces.c holds their external definitions). */
+#if defined(__HIPCC__)
+#define XG_HD __host__ __device__
+#else
+#define XG_HD
+#endif
+typedef struct { uint32_t copy; int64_t off, n; } xg_small_at;
+inline XG_HD uint32_t xg_small_ppc(int64_t len, int64_t piece) { return (uint32_t)((len + piece - 1) / piece); }
+inline XG_HD xg_small_at xg_small_index(uint32_t b, uint32_t copies, int64_t len, int64_t piece, uint32_t k)
+{
+    const uint32_t gs = k * xg_small_ppc(len, piece);      /* workgroups of a full group */
+    const uint32_t g = b / gs, r = b - g * gs;
+    const uint32_t left = copies - g * k, kk = left < k ? left : k;
+    const uint32_t j = r / kk;
+    xg_small_at a;
+    a.copy = g * k + (r - j * kk);
+    a.off = (int64_t)j * piece;
+    a.n = len - a.off < piece ? len - a.off : piece;
+    return a;
+}
+/* xg_small_index for callers that cannot inline it (pieces.c); returns 0, or -1 when b is not a
+ * workgroup of the launch or an argument is out of range. */
+int xg_small_piece_at(int64_t b, int64_t copies, int64_t len, int64_t piece, int k, int64_t *copy, int64_t *off,
+                      int64_t *n);
+
 /* ---------------------------------------------------------------- placement (place.c)
  * Where the segments of an exchange lie in the aggregators' collective buffers (ROMIO's
  * others_req[i].offsets / lens): a list of n extents describes the whole job, and every rank

@@ -64,6 +64,26 @@ int xg_extent_tiles(const int64_t *lens, int n, int64_t tile_bytes, int tile_pie
     return nt;
 }
 
+/* the external definitions of xg_sched.h's inline index functions */
+extern inline uint32_t xg_small_ppc(int64_t len, int64_t piece);
+extern inline xg_small_at xg_small_index(uint32_t b, uint32_t copies, int64_t len, int64_t piece, uint32_t k);
+
+/* Workgroup b of a small-piece launch (xg_small_index, xg_sched.h), range-checked. */
+int xg_small_piece_at(int64_t b, int64_t copies, int64_t len, int64_t piece, int k, int64_t *copy, int64_t *off,
+                      int64_t *n)
+{
+    xg_small_at a;
+    if (b < 0 || copies < 1 || len < 1 || piece < 1 || k < 1 || k > (1 << 20)) return -1;
+    if (copies * (int64_t)xg_small_ppc(len, piece) > INT32_MAX || (int64_t)k * xg_small_ppc(len, piece) > INT32_MAX ||
+        b >= copies * (int64_t)xg_small_ppc(len, piece))
+        return -1;
+    a = xg_small_index((uint32_t)b, (uint32_t)copies, len, piece, (uint32_t)k);
+    if (copy) *copy = a.copy;
+    if (off) *off = a.off;
+    if (n) *n = a.n;
+    return 0;
+}
+
 /* [off, end) of region buf */
 typedef struct { int64_t lo, hi; } ival;
 

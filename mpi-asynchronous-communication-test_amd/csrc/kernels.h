@@ -16,6 +16,8 @@
 //                     out of RCCL staging).  Replaces the shared-memory copies MPI
 //                     does inside Irecv/Issend/Alltoallw.  Misaligned pieces (-d not
 //                     a multiple of 16) are realigned through LDS.
+//  copy_kernel_q      a large uniform launch in 4 / 8 KiB pieces: one table row per copy, the piece
+//                     found by index arithmetic, straight-line buffer loads then stores.
 //  copy_kernel_s      the copy of a ragged exchange: one workgroup per piece at any source
 //                     phase, destination phase and length; aligned 16-B buffer loads of the
 //                     two granules a lane's 16 bytes straddle, funnel shift in registers.
@@ -33,6 +35,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+
+#include "../../include/xg_sched.h"     // xg_small_index: the one host / device function of this file
 
 namespace xgk {
 
@@ -365,6 +369,33 @@ __global__ __launch_bounds__(kThreads) void copy_kernel_w(const DCopy *__restric
         store(b, pb);
         if (k + 2 >= n) break;
     }
+}
+
+// Straight-line streaming copy of a UNIFORM launch in small pieces: copy_kernel_q<L, NT>.  The
+// launch is `copies` table rows {src, dst, len} -- one per COPY, every len the same, everything
+// 16-B aligned -- and one workgroup per piece of L * 4 KiB: workgroup base + blockIdx.x finds its
+// row and offset by arithmetic (xg_small_index, xg_sched.h; every operand workgroup-uniform, so
+// the row comes by one scalar load) instead of from a per-piece descriptor.  Each lane issues its
+// L 16-B buffer loads, then its L stores: no loop, no LDS, no realign path.  The piece's length is
+// the range of its two buffer resources, so a copy's short last piece needs no branch (loads past
+// it return 0, stores past it are dropped).  `base`: the first workgroup of this dispatch (a launch
+// cut into dispatches, XG_COPY_LAUNCH_MAX, may be cut inside a copy).  NT, start: as copy_kernel_g.
+template <int L, bool NT = false>
+__global__ __launch_bounds__(kThreads) void copy_kernel_q(const DCopy *__restrict__ rows, uint32_t base,
+                                                          uint32_t copies, int64_t len, uint32_t k,
+                                                          unsigned long long *start)
+{
+    constexpr int AUX = NT ? kAuxNT : kAuxPlain;
+    if (start && blockIdx.x == 0 && threadIdx.x == 0) *start = (unsigned long long)wall_clock64();
+    const xg_small_at a = xg_small_index(base + blockIdx.x, copies, len, (int64_t)L * kTile, k);
+    const DCopy c = rows[__builtin_amdgcn_readfirstlane((int)a.copy)];
+    const brsrc rs = make_rsrc(c.src + a.off, a.n), rd = make_rsrc(c.dst + a.off, a.n);
+    const int o = (int)threadIdx.x * 16;
+    u32x4 v[L];
+#pragma unroll
+    for (int j = 0; j < L; ++j) v[j] = bload16a<AUX>(rs, o + j * kTile);
+#pragma unroll
+    for (int j = 0; j < L; ++j) bstore16<AUX>(rd, o + j * kTile, v[j]);
 }
 
 // the wall clock after everything before it on the stream: closes a chain of step launches

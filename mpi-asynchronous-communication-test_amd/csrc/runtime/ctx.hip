@@ -207,6 +207,21 @@ static int init_ctx(xg_ctx *c, const void *uid)
     c->extent_tile = kExtTileBytes;
     env = getenv("XG_EXTENT_TILE_KIB");
     if (env && atoi(env) > 0 && atoi(env) <= 1024) c->extent_tile = (int64_t)atoi(env) << 10;
+    // copy_kernel_q for large uniform launches (TableBuilder::open): "0" restores copy_kernel_g's
+    // 32 KiB pieces.  XG_SMALL_PIECE_MIN: test hook, the launch size it starts at;
+    // XG_SMALL_PIECE_KIB (4 / 8) and XG_SMALL_PIECE_ORDER (copies per group of the piece order):
+    // for the A/B of profiles/small_pieces_ab.sh
+    env = getenv("XG_SMALL_PIECES");
+    c->small_pieces = env ? atoi(env) != 0 : kSmallDefault;
+    c->small_piece_min = kSmallMin;
+    env = getenv("XG_SMALL_PIECE_MIN");
+    if (env && atoll(env) >= 0) c->small_piece_min = atoll(env);
+    c->small_kib = kSmallKiB;
+    env = getenv("XG_SMALL_PIECE_KIB");
+    if (env && (atoi(env) == 4 || atoi(env) == 8)) c->small_kib = atoi(env);
+    c->small_order = kSmallOrder;
+    env = getenv("XG_SMALL_PIECE_ORDER");
+    if (env && atoi(env) >= 1 && atoi(env) <= 1024) c->small_order = atoi(env);
     c->engine_max_step = 16 << 20;    // crossover vs one launch per step: profiles/r01_engine_sweep.txt
     env = getenv("XG_ENGINE_MAX_STEP");      // 0: never use the step engine
     if (env) c->engine_max_step = atol(env);

@@ -55,7 +55,13 @@ static int wave_wgs(const xg_plan *p, int n) { return std::max(1, std::min(p->ct
 static int launch_one(xg_plan *p, const CopyLaunch &l, int b, int n, hipStream_t st, unsigned long long *start)
 {
     const xgk::DCopy *pc = p->d_pieces + b;
-    if (l.kib && b == l.b) {
+    if (l.q) {
+        // workgroups [b, b + n) of the launch, each finding its piece of the launch's rows
+        const auto k = l.q == 1 ? (l.nt ? xgk::copy_kernel_q<1, true> : xgk::copy_kernel_q<1, false>)
+                                : (l.nt ? xgk::copy_kernel_q<2, true> : xgk::copy_kernel_q<2, false>);
+        hipLaunchKernelGGL(k, dim3(n), dim3(xgk::kThreads), 0, st, p->d_rows + l.q_row, (uint32_t)b,
+                           (uint32_t)l.q_copies, l.q_len, (uint32_t)l.q_k, start);
+    } else if (l.kib && b == l.b) {
         const auto k = l.kib == 2   ? xgk::copy_kernel_w<2>
                        : l.kib == 4 ? xgk::copy_kernel_w<4>
                                     : xgk::copy_kernel_w<xgk::kWaveKiB>;
@@ -107,7 +113,7 @@ static int launch_copy(xg_plan *p, const CopyLaunch &l, hipStream_t st, unsigned
     const int *cut = p->cuts.data() + l.cut;
     int rc;
     for (int k = 0; k < l.ndisp; ++k) {
-        const int64_t nb = l.ndisp == 1 ? l.bytes : p->plen[cut[k + 1]] - p->plen[cut[k]];
+        const int64_t nb = l.q ? p->qbytes[l.q_bytes + k] : l.ndisp == 1 ? l.bytes : p->plen[cut[k + 1]] - p->plen[cut[k]];
         bool kt;
         if ((rc = kt_before(p->ctx, st, &kt))) return rc;
         if ((rc = launch_one(p, l, cut[k], cut[k + 1] - cut[k], st, k == 0 ? start : nullptr))) return rc;
@@ -174,6 +180,19 @@ extern "C" int xg_plan_shift_launches(const xg_plan *p)
 {
     int count = 0;
     each_launch(p, [&](const CopyLaunch &l) { count += l.shift; });
+    return count;
+}
+
+// ... those that go to copy_kernel_q, the small-piece copy of large uniform launches (*kib: their
+// piece size, 0 when there is none; may be NULL) ...
+extern "C" int xg_plan_small_launches(const xg_plan *p, int *kib)
+{
+    int count = 0, q = 0;
+    each_launch(p, [&](const CopyLaunch &l) {
+        count += l.q != 0;
+        if (l.q) q = l.q;
+    });
+    if (kib) *kib = 4 * q;
     return count;
 }
 

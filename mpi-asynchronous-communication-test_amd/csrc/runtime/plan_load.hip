@@ -15,7 +15,7 @@ static uint64_t next_plan_id()
 static bool engine_step(const xg_ctx *c, const StepR &st)
 {
     return !st.p2p_n && !st.sync_after && !st.stage_n && !st.stage_fused && !st.post_n && !st.pack_n && !st.fused &&
-           !st.deferred && st.local_bytes <= c->engine_max_step;
+           !st.deferred && !st.small && st.local_bytes <= c->engine_max_step;
 }
 
 // Build the engine segments of a loaded plan from its host piece table: every
@@ -523,7 +523,14 @@ struct TableBuilder {
     // `reread` (copy_variant) comes twice: for the cut of the pieces and for the kernel.  They
     // differ in one launch only (step(), the local + pack launch); where the cut says plain and
     // the kernel non-temporal, the wave-sized pieces run copy_kernel_g<4, true>.
-    void open(CopyLaunch &l, std::initializer_list<Range> ranges, bool cross, bool reread_cut, bool reread_run)
+    // `may_small`: a step's own local (+ pack) launch.  When it is UNIFORM -- every positive copy the
+    // same length --, 16-B aligned, holds no pack (a pack's staging side is patched per piece by the
+    // device scan), would run copy_kernel_g<4> and moves >= small_piece_min bytes, it runs
+    // copy_kernel_q instead: pieces of small_kib KiB found by index arithmetic, its copies listed as
+    // rows (add), no piece cut at all.  The bench's 448 MiB launches: 114,688 / 57,344 workgroups
+    // from 448 rows.  XG_SMALL_PIECES=0: never.
+    void open(CopyLaunch &l, std::initializer_list<Range> ranges, bool cross, bool reread_cut, bool reread_run,
+              bool may_small = false)
     {
         const xg_ctx *c = p->ctx;
         cur = &l;
@@ -564,8 +571,37 @@ struct TableBuilder {
         } else {
             chunk = xg_piece_size(lens.data(), (int)lens.size(), c->chunk, c->cus, kWgCost);
         }
+        if (!may_small || !c->small_pieces || l.ext || l.shift || l.kib || !l.stamps || (bits & 15) != 0 ||
+            l.bytes < c->small_piece_min)
+            return;
+        int64_t len = 0;
+        bool uniform = true;
+        for (const Range &rg : ranges)
+            for (int i = 0; i < rg.second; ++i) {
+                const xg_copy &cp = dp->copies[rg.first + i];
+                if (cp.len <= 0) continue;
+                uniform = uniform && (len == 0 || cp.len == len) && cp.dst_buf != XG_BUF_STAGE_SEND &&
+                          cp.src_buf != XG_BUF_STAGE_RECV;
+                len = cp.len;
+            }
+        const int64_t piece = (int64_t)c->small_kib << 10;
+        const int64_t ppc = (len + piece - 1) / piece;
+        // xg_small_index works in 32 bits: the launch's workgroups and a group's
+        if (!uniform || npos * ppc > INT32_MAX || c->small_order * ppc > INT32_MAX) return;
+        l.q = c->small_kib / 4;
+        l.q_len = len;
+        l.q_k = c->small_order;
+        l.q_row = (int)p->rows.size();
     }
-    void close() { cur->n = (int)pieces.size() - cur->b; }
+    // a copy_kernel_q launch: its rows in destination order (order_pieces, for a launch without pieces)
+    void close()
+    {
+        cur->n = (int)pieces.size() - cur->b;
+        if (!cur->q) return;
+        cur->q_copies = (int)p->rows.size() - cur->q_row;
+        std::stable_sort(p->rows.begin() + cur->q_row, p->rows.end(),
+                         [](const xgk::DCopy &x, const xgk::DCopy &y) { return x.dst < y.dst; });
+    }
 
     // side: -1 plain copy; 0 pack (destination in STAGE_SEND, displacement from the
     // device scan); 1 unpack (source in STAGE_RECV, likewise)
@@ -577,6 +613,10 @@ struct TableBuilder {
         if (cp.src_off < 0 || cp.dst_off < 0 || cp.src_off + cp.len > r->bytes[cp.src_buf] ||
             cp.dst_off + cp.len > r->bytes[cp.dst_buf])
             return false;
+        if (cur->q) {        // one row per copy; the kernel cuts it (open() let no pack or unpack in)
+            p->rows.push_back({r->ptr[cp.src_buf] + cp.src_off, r->ptr[cp.dst_buf] + cp.dst_off, cp.len});
+            return side < 0;
+        }
         const int ci = (int)ds.len.size();
         if (side >= 0) {
             ds.len.push_back(cp.len);
@@ -660,18 +700,22 @@ struct TableBuilder {
                 local.mark_prev = true;
                 if (!add_post(s - 1)) return false;
             } else if (st.split) {
-                open(local, {r_local}, true, false, false);
+                open(local, {r_local}, true, false, false, true);
                 local.side = true;
             } else if (!st.fused) {
                 // the cut asks whether the step lists packs, the kernel whether any holds bytes:
                 // they part for a step whose packs are all empty
-                open(local, {r_local, r_pack}, cross, r_pack.second > 0, bytes_of(r_pack) > 0);
+                open(local, {r_local, r_pack}, cross, r_pack.second > 0, bytes_of(r_pack) > 0, true);
             }
         }
         st.local_b = st.stage_fused ? st.stage_b : (int)pieces.size();
         if (!add_range(r_local, -1)) return false;
         st.local_n = (int)pieces.size() - st.local_b;
         st.local_bytes = span(st.local_b);
+        if (local.q) {       // rows, not pieces
+            st.small = true;
+            st.local_bytes = local.bytes;
+        }
         if (st.split || (st.fused && !st.fused_local)) {
             if (st.split) close();
             open(pack, {r_prev, r_pack}, true, true, true);
@@ -697,7 +741,7 @@ struct TableBuilder {
         // of sharing HBM with the packs (XG_SPLIT_AFTER_PACK=0: both at once, as in round 2)
         std::vector<CopyLaunch> &tab = p->launches;
         auto push = [&](const CopyLaunch &l) {
-            if (l.n > 0) tab.push_back(l);
+            if (l.n > 0 || l.q) tab.push_back(l);
         };
         const bool pack_first = st.fused || c->split_after_pack;
         st.l_b = (int)tab.size();
@@ -751,6 +795,31 @@ static void order_pieces(const xg_plan *p, std::vector<xgk::DCopy> &pieces, Disp
     }
 }
 
+// The dispatches of a copy_kernel_q launch: its cuts are workgroup indices (0 .. its workgroups), a
+// dispatch is about launch_max bytes of whole pieces -- a cut may fall inside a copy, the kernel
+// takes the dispatch's first workgroup as `base` -- and no runt dispatch closes the launch.  The
+// bytes of each dispatch (kernel-timing sessions) are summed here once, through the index function.
+static void cut_small(xg_plan *p, CopyLaunch &l)
+{
+    const int64_t cap = p->ctx->launch_max, piece = (int64_t)l.q * xgk::kTile;
+    const int64_t W = (int64_t)l.q_copies * xg_small_ppc(l.q_len, piece);
+    l.cut = (int)p->cuts.size();
+    p->cuts.push_back(0);
+    if (cap > 0 && l.bytes > cap + cap / 2) {
+        const int64_t per = std::max<int64_t>(1, cap / piece);
+        for (int64_t o = per; o < W && (W - o) * piece >= cap / 2 && W - o >= 16; o += per) p->cuts.push_back((int)o);
+    }
+    p->cuts.push_back((int)W);
+    l.ndisp = (int)p->cuts.size() - 1 - l.cut;
+    l.q_bytes = (int)p->qbytes.size();
+    for (int k = 0; k < l.ndisp; ++k) {
+        int64_t nb = 0;
+        for (int64_t b = p->cuts[l.cut + k]; b < p->cuts[l.cut + k + 1]; ++b)
+            nb += xg_small_index((uint32_t)b, (uint32_t)l.q_copies, l.q_len, piece, (uint32_t)l.q_k).n;
+        p->qbytes.push_back(nb);
+    }
+}
+
 // Each launch's dispatches.  A launch of more than 1.5 x launch_max bytes goes as back-to-back
 // kernel dispatches of about launch_max bytes each (its pieces are independent: the same step,
 // a few more kernel boundaries).  P256 A32 -d 4 MiB m1 / m2 (one 32 GiB step, 1 M pieces):
@@ -762,6 +831,10 @@ static void cut_launches(xg_plan *p)
     const int64_t cap = p->ctx->launch_max;
     const int64_t *pre = p->plen.data();        // prefix sums of the piece lengths
     for (CopyLaunch &l : p->launches) {
+        if (l.q) {
+            cut_small(p, l);
+            continue;
+        }
         const int end = l.b + l.n;
         l.cut = (int)p->cuts.size();
         p->cuts.push_back(l.b);
@@ -841,6 +914,10 @@ static int plan_upload(xg_plan *p, const std::vector<xgk::DCopy> &pieces, DisplS
     if (p->npieces) {
         HIPCHK(hipMalloc(&p->d_pieces, sizeof(xgk::DCopy) * pieces.size()));
         HIPCHK(hipMemcpy(p->d_pieces, pieces.data(), sizeof(xgk::DCopy) * pieces.size(), hipMemcpyHostToDevice));
+    }
+    if (!p->rows.empty()) {
+        HIPCHK(hipMalloc(&p->d_rows, sizeof(xgk::DCopy) * p->rows.size()));
+        HIPCHK(hipMemcpy(p->d_rows, p->rows.data(), sizeof(xgk::DCopy) * p->rows.size(), hipMemcpyHostToDevice));
     }
     if (!p->xt_begin.empty()) {
         HIPCHK(hipMalloc(&p->d_xt, sizeof(int) * p->xt_begin.size()));
@@ -925,7 +1002,8 @@ extern "C" int xg_plan_free(xg_plan *p)
     keep(hipStreamSynchronize(p->ctx->stream));
     keep(hipStreamSynchronize(p->ctx->side));
     for (void *q : {(void *)p->d_pieces, (void *)p->d_sb, (void *)p->d_epieces, (void *)p->d_engine,
-                    (void *)p->d_disp, (void *)p->d_solo, (void *)p->d_cstamp, (void *)p->d_gstamp, (void *)p->d_xt})
+                    (void *)p->d_disp, (void *)p->d_solo, (void *)p->d_cstamp, (void *)p->d_gstamp, (void *)p->d_xt,
+                    (void *)p->d_rows})
         if (q) keep(hipFree(q));
     if (p->db) keep(hipHostFree((void *)p->db));
     for (auto &e : p->fork) if (e) keep(hipEventDestroy(e));

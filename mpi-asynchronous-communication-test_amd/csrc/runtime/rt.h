@@ -148,6 +148,10 @@ struct xg_ctx {
     int64_t extent_mean_max;   // ... when the launch's mean positive copy length is <= this (kExtMeanMax)
     int64_t extent_tile;       // bytes per copy_kernel_x tile (kExtTileBytes)
     int engine_occ;            // co-resident step-engine workgroups the device admits (plan load caps W)
+    int small_pieces;          // 1: large uniform launches run copy_kernel_q (XG_SMALL_PIECES; TableBuilder::open)
+    int64_t small_piece_min;   // ... from this many bytes up (kSmallMin; XG_SMALL_PIECE_MIN, a test hook, lowers it)
+    int small_kib;             // their piece size, 4 or 8 KiB (kSmallKiB; XG_SMALL_PIECE_KIB, for the A/B)
+    int small_order;           // copies per group of their piece order (xg_small_index's k; XG_SMALL_PIECE_ORDER, A/B)
     // kernel timing session (xg_ktime_begin/end): 1 = an event pair around every
     // copy launch, 2 = one pair around the whole session on the main stream
     int kt_mode;
@@ -179,6 +183,13 @@ struct CopyLaunch {
                                      // (XG_DP_EXTENTS; TableBuilder::open), one workgroup per TILE of pieces:
                                      // dispatch k's tiles are xg_plan::xt_begin[xt_off[xt + k] ..], xt_n[xt + k] of them
     int xt = 0;
+    int q = 0;                       // 1 / 2: copy_kernel_q<q, nt> -- a uniform, aligned launch in pieces of q x 4 KiB
+                                     // (TableBuilder::open).  It has NO pieces (n = 0): its copies are rows
+                                     // [q_row, q_row + q_copies) of xg_plan::d_rows, each q_len bytes, taken q_k to
+                                     // a group (xg_small_index); its cuts are workgroup indices from 0, and
+                                     // dispatch k copies xg_plan::qbytes[q_bytes + k] bytes
+    int q_row = 0, q_copies = 0, q_k = 1, q_bytes = 0;
+    int64_t q_len = 0;
     bool stamps = false;             // its kernel can stamp its start (a chain step's launch must)
     bool side = false;               // runs on the side stream: fork event before it, join event after it
     bool mark_prev = false;          // holds the previous step's unpacks: that step's mark goes right behind it
@@ -204,6 +215,8 @@ struct StepR {
     int pre_n = 0;                   // local_n + pack_n
     int64_t stage_bytes = 0, local_bytes = 0, pack_bytes = 0, post_bytes = 0;   // bytes copied by each part (read + written once)
     bool split = false, fused = false, deferred = false;
+    bool small = false;              // its local launch runs copy_kernel_q: it has rows, no pieces (local_n = 0),
+                                     // and is never an engine step
     bool self_local = false;         // the local copies travel in the RCCL group as self send/recv (XG_SELF_MAX)
     bool fused_local = false;        // fused, and the local copies join that launch (small, hazard-free)
     bool stage_fused = false;        // the stage copies join the step's local (+ pack) launch: none of the
@@ -253,6 +266,11 @@ struct xg_plan {
     // of the dispatch (indices relative to its first piece); d_xt: xt_begin on the device
     std::vector<int> xt_begin, xt_off, xt_n;
     int *d_xt = nullptr;
+    // copy_kernel_q launches: one row {src, dst, len} per positive copy, in destination order
+    // (CopyLaunch::q_row), and the bytes of each of their dispatches (CopyLaunch::q_bytes)
+    std::vector<xgk::DCopy> rows;
+    xgk::DCopy *d_rows = nullptr;
+    std::vector<int64_t> qbytes;
     std::vector<hipEvent_t> fork, join;     // per step with a side-stream launch: main -> side, side -> main
     int variant = 0;
     bool streaming = false;                 // one run copies more than the Infinity Cache holds (read + write)
@@ -353,6 +371,18 @@ constexpr int64_t kExtTileBytes = 32 << 10;
 constexpr int kExtTilePieces = xgk::kThreads;
 constexpr int64_t kExtMeanMax = 1024;
 constexpr int kExtDefault = 1;
+// copy_kernel_q: the launch size from which a uniform launch runs it, its piece KiB, the copies
+// per group of its piece order (xg_small_index's k: with 8, the eight workgroups that start
+// together walk eight consecutive destination copies side by side, one piece each per round) and
+// whether it runs at all without XG_SMALL_PIECES.  Chosen by bench.py's CHOICE_RULE over the arms of
+// profiles/r10/small_pieces/ab.txt: 8 KiB x 8 copies -5 % against the
+// parent's 32 KiB pieces; 8 KiB in plain destination order (k = 1) a tie, 4 KiB slower.  The
+// threshold is the smallest launch of the size sweep (size_sweep.txt: 28 MiB - 896 MiB) that won by
+// the rule: 112 MiB -7 %, 224 MiB -5 %, 896 MiB -4 %; 56 MiB -3 % (inside the spread), 28 MiB +1 %.
+constexpr int64_t kSmallMin = 112 << 20;
+constexpr int kSmallKiB = 8;
+constexpr int kSmallOrder = 8;
+constexpr int kSmallDefault = 1;
 constexpr int64_t kWaveMax = 32 << 20;     // copy_kernel_w up to this launch size (profiles/r03/wave_local/)
 // Piece KiB of a copy_kernel_w launch of `bytes`: the largest of 8 / 4 / 2 that still gives every
 // CU a 4-wave workgroup (bytes / piece >= 4 x CUs): a 4 MiB launch in 8 KiB pieces is 512 waves =

@@ -36,6 +36,11 @@
 //   kind 36 <4, plain, nt>                          kind 37 <4, nt, plain>
 //   kind 38 the contiguous copy (kind 9's pieces) as copy_kernel_bb<4, nt, nt|sc1>
 //   kind 39 the kind-16 gather, copy_kernel_bb<4, nt|sc1, nt|sc1>
+//   round 10, copy_kernel_q<L, nt> (L x 4 KiB pieces found by index arithmetic from one row per
+//   1 MiB copy, k copies to a group of the piece order: xg_small_index):
+//   kind 40 the contiguous copy, 4 KiB, k = 1   kind 41 8 KiB, k = 1   kind 42 8 KiB, k = 8
+//   kind 43 the kind-16 gather, 4 KiB, k = 1    kind 44 8 KiB, k = 1   kind 45 8 KiB, k = 8
+//   kind 46 the kind-16 gather, 4 KiB, k = 8
 // *gbps = counted bytes / average launch time (a copy counts read + write).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -219,7 +224,7 @@ __global__ __launch_bounds__(xgk::kThreads) void gridstride_copy_mix(const xgk::
 extern "C" int xgt_copy_ceiling(int device, int64_t bytes, int kind, int reps, double *gbps)
 {
     bytes &= ~(int64_t)32767;
-    if (bytes <= 0 || reps < 1 || kind < 0 || kind > 39) return 3;
+    if (bytes <= 0 || reps < 1 || kind < 0 || kind > 46) return 3;
     CK(hipSetDevice(device));
     hipStream_t st;
     CK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -233,7 +238,16 @@ extern "C" int xgt_copy_ceiling(int device, int64_t bytes, int kind, int reps, d
                         : kind == 7 ? 262144 : kind == 8 ? 65536 : kind == 22 || kind == 23 || kind == 27 ? 8192 : kind == 24 ? 4096
                         : kind == 25 ? 16384 : kind >= 18 ? 16384 : 32768;
     std::vector<xgk::DCopy> pieces;
-    if (kind == 16 || kind == 17 || kind == 23 || kind == 24 || kind == 25 || (kind >= 28 && kind != 38)) {   // bytes ignored: 14 x 32 one-MiB segments
+    if (kind >= 40) {      // rows, not pieces: one per 1 MiB copy, in destination order
+        const int64_t seg = 1 << 20, stride = 32 * seg;
+        if (kind >= 43 ? 14 * stride > bytes : bytes % seg != 0) return 3;
+        if (kind >= 43) {
+            for (int r = 0; r < 32; ++r)
+                for (int g = 0; g < 14; ++g) pieces.push_back({a + g * stride + r * seg, b + (int64_t)(r * 14 + g) * seg, seg});
+        } else {
+            for (int64_t o = 0; o < bytes; o += seg) pieces.push_back({a + o, b + o, seg});
+        }
+    } else if (kind == 16 || kind == 17 || kind == 23 || kind == 24 || kind == 25 || (kind >= 28 && kind != 38)) {   // bytes ignored: 14 x 32 one-MiB segments
         const int64_t seg = 1 << 20, stride = 32 * seg + (kind == 17 ? 65536 : 0);
         if (14 * stride > bytes) return 3;
         for (int r = 0; r < 32; ++r)
@@ -277,7 +291,7 @@ extern "C" int xgt_copy_ceiling(int device, int64_t bytes, int kind, int reps, d
     if (kind == 25) CK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, xgk::copy_kernel_w<16, true>, xgk::kThreads, 0));
     CK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     const unsigned wgrid = (unsigned)std::max(1, std::min<int>(occ * cus, ((int)np + 3) / 4));
-    if (kind >= 22 && kind != 26) fprintf(stderr, "xgt kind %d: %u pieces, %d resident workgroups per CU -> grid %u\n", kind, np, occ, wgrid);
+    if (kind >= 22 && kind != 26 && kind < 40) fprintf(stderr, "xgt kind %d: %u pieces, %d resident workgroups per CU -> grid %u\n", kind, np, occ, wgrid);
     for (int r = -2; r < reps; ++r) {          // 2 warm-up launches
         if (r == 0) CK(hipEventRecord(e0, st));
         switch (kind) {
@@ -329,6 +343,15 @@ extern "C" int xgt_copy_ceiling(int device, int64_t bytes, int kind, int reps, d
         case 37: hipLaunchKernelGGL((copy_kernel_bb<4, 2, 0>), dim3(np), dim3(xgk::kThreads), 0, st, dp); break;
         case 38: hipLaunchKernelGGL((copy_kernel_bb<4, 2, 18>), dim3(np), dim3(xgk::kThreads), 0, st, dp); break;
         case 39: hipLaunchKernelGGL((copy_kernel_bb<4, 18, 18>), dim3(np), dim3(xgk::kThreads), 0, st, dp); break;
+        case 40:
+        case 43:
+        case 46: hipLaunchKernelGGL((xgk::copy_kernel_q<1, true>), dim3(np * 256), dim3(xgk::kThreads), 0, st, dp, 0u, np,
+                                    (int64_t)1 << 20, kind == 46 ? 8u : 1u, nullptr); break;
+        case 41:
+        case 42:
+        case 44:
+        case 45: hipLaunchKernelGGL((xgk::copy_kernel_q<2, true>), dim3(np * 128), dim3(xgk::kThreads), 0, st, dp, 0u, np,
+                                    (int64_t)1 << 20, kind == 42 || kind == 45 ? 8u : 1u, nullptr); break;
         default: hipLaunchKernelGGL((xgk::copy_kernel_g<4>), dim3(np), dim3(xgk::kThreads), 0, st, dp, nullptr); break;
         }
         CK(hipGetLastError());
@@ -337,7 +360,8 @@ extern "C" int xgt_copy_ceiling(int device, int64_t bytes, int kind, int reps, d
     CK(hipEventSynchronize(e1));
     float ms = 0;
     CK(hipEventElapsedTime(&ms, e0, e1));
-    const double moved = kind == 16 || kind == 17 || (kind >= 23 && kind <= 25) || (kind >= 28 && kind != 38) ? 448.0 * (1 << 20) : kind >= 18 ? 28.0 * (1 << 20)
+    const double moved = kind >= 40 && kind <= 42 ? (double)bytes
+                         : kind == 16 || kind == 17 || (kind >= 23 && kind <= 25) || (kind >= 28 && kind != 38) ? 448.0 * (1 << 20) : kind >= 18 ? 28.0 * (1 << 20)
                                                                                                : (double)bytes;
     *gbps = (kind == 3 || kind == 4 || kind == 10 || kind == 11 ? 1.0 : 2.0) * moved * reps / (ms * 1e-3) / 1e9;
     CK(hipEventDestroy(e0));

@@ -203,6 +203,7 @@ def host():
         h.xg_piece_size.restype = C.c_int64
         h.xg_piece_size.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_int, C.c_int64]
         h.xg_extent_tiles.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int32)]
+        h.xg_small_piece_at.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int] + [C.POINTER(C.c_int64)] * 3
         h.xg_exts_lens.argtypes = [C.POINTER(Ext), C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]
         h.xg_exts_check.argtypes = [C.POINTER(Ext), C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int,
                                     C.c_char_p, C.c_size_t]
@@ -351,6 +352,16 @@ def extent_tiles(lens, tile_bytes=32768, tile_pieces=256):
     begin = (C.c_int32 * (nt + 1))()
     assert host().xg_extent_tiles(arr, n, tile_bytes, tile_pieces, begin) == nt
     return list(begin)
+
+
+def small_piece_at(b, copies, length, piece, k=1):
+    """xg_small_piece_at: (copy, offset, bytes) of workgroup b of a small-piece launch (copy_kernel_q) over
+    `copies` copies of `length` bytes in pieces of `piece` bytes, k copies to a group; None when b is
+    no workgroup of it"""
+    out = [C.c_int64() for _ in range(3)]
+    if host().xg_small_piece_at(b, copies, length, piece, k, *[C.byref(x) for x in out]) != 0:
+        return None
+    return tuple(x.value for x in out)
 
 
 def _ext_array(exts):
@@ -723,6 +734,7 @@ def device():
         d.xg_plan_wave_launches.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
         d.xg_plan_shift_launches.argtypes = [vp]
         d.xg_plan_extent_launches.argtypes = [vp]
+        d.xg_plan_small_launches.argtypes = [vp, C.POINTER(ip)]
         d.xg_exchange_w.argtypes = [vp, ip, ip, ip, C.POINTER(Ext), i64, C.POINTER(i64), C.POINTER(ip), ip, vp, vp,
                                     C.POINTER(Timer), ip, ip, C.POINTER(RunOpts), C.POINTER(i64), C.POINTER(i64),
                                     C.POINTER(C.c_double), C.c_char_p, C.c_size_t]

@@ -17,7 +17,9 @@ names = {0: "grid-stride copy", 1: "copy_kernel_g<4> 32K", 2: "copy_kernel_b<4,s
          28: "m2a g<4,nt> 64K", 29: "m2a g<8,nt> 32K", 30: "m2a g<4,nt> 128K", 31: "m2a g<4,nt> 16K",
          32: "m2a bb ld nt st nt", 33: "m2a bb ld nt st nt|sc1", 34: "m2a bb nt|sc0|sc1 both",
          35: "m2a bb ld nt st sc0|sc1", 36: "m2a bb ld plain st nt", 37: "m2a bb ld nt st plain",
-         38: "contig bb ld nt st nt|sc1", 39: "m2a bb nt|sc1 both"}
+         38: "contig bb ld nt st nt|sc1", 39: "m2a bb nt|sc1 both", 40: "contig q<1,nt> 4K k1", 41: "contig q<2,nt> 8K k1",
+         42: "contig q<2,nt> 8K k8", 43: "m2a q<1,nt> 4K k1", 44: "m2a q<2,nt> 8K k1", 45: "m2a q<2,nt> 8K k8",
+         46: "m2a q<1,nt> 4K k8"}
 kinds = [int(k) for k in os.environ.get("KINDS", "0,1,2,3,4,5,6,7,8,9").split(",")]
 sizes = [int(x) << 20 for x in os.environ.get("SIZES_MIB", "448,1024,4096").split(",")]
 for nb in sizes:
