@@ -153,7 +153,8 @@ int xg_plan_check(xg_plan *p);
  * barrier, no unpack, each <= XG_ENGINE_MAX_STEP bytes; 0 = off) is ONE persistent
  * launch of up to one workgroup per CU (fewer if the device admits fewer), grid barrier +
  * wall-clock stamp per step; the other steps are their own launches.
- * Small hazard-free segments run on the solo engine instead: each step's pieces
+ * Small hazard-free segments in which no step reads what another step writes
+ * (xg_engine_rail_safe) run on the solo engine instead: each step's pieces
  * dealt over up to XG_SOLO_RAILS independent rails (default 512 rails of one wave;
  * XG_SOLO_WAVES=16: 16-wave workgroups) that each keep their own step order and
  * never wait for one another.

@@ -327,6 +327,12 @@ int64_t xg_devplans_match(const xg_devplan *const *plans, int ngpus, int64_t sel
  * Returns the number of hazard points (flag 2). */
 typedef struct { uint64_t src, dst, len; } xg_span;
 int xg_engine_hazards(const xg_span *xfer, const int *step_begin, int nsteps, int force, int *flags);
+/* May these steps run on the solo engine's rails, which never wait for each other (no
+ * ordering between steps at all, unlike the grid engine's barrier)?  1 if no transfer's
+ * source range meets the destination range of a transfer of another step, in either step
+ * order -- so write-after-read, which gets no flag above, is excluded too; 0 otherwise.
+ * A rail segment needs this AND no hazard point. */
+int xg_engine_rail_safe(const xg_span *xfer, const int *step_begin, int nsteps);
 
 /* Solo engine tables of one hazard-free run of steps (xg.h XG_SOLO_RAILS; kernels.h
  * solo_engine_kernel, whose constants must equal these).  Pieces of <= XG_SOLO_PIECE

@@ -55,24 +55,33 @@ static int meets(const ivl *v, int n, uint64_t a, uint64_t b, int want, int64_t 
     return 0;
 }
 
+/* 1 if the hull of every source range and the hull of every destination range are disjoint
+ * (every SEND -> RECV plan): then no transfer reads a byte that any transfer writes.  *m: the
+ * transfers that move bytes. */
+static int hulls_disjoint(const xg_span *xfer, int n, int *m)
+{
+    uint64_t slo = UINT64_MAX, shi = 0, dlo = UINT64_MAX, dhi = 0;
+    int i;
+    for (i = 0, *m = 0; i < n; ++i)
+        if (xfer[i].len) {
+            if (xfer[i].src < slo) slo = xfer[i].src;
+            if (xfer[i].src + xfer[i].len > shi) shi = xfer[i].src + xfer[i].len;
+            if (xfer[i].dst < dlo) dlo = xfer[i].dst;
+            if (xfer[i].dst + xfer[i].len > dhi) dhi = xfer[i].dst + xfer[i].len;
+            ++*m;
+        }
+    return !*m || !(slo < dhi && dlo < shi);
+}
+
 /* Fast path, O(N log N) once: when no transfer reads bytes that any transfer writes (the
  * source and destination hulls are disjoint, as for every SEND -> RECV plan) and no two
  * writes of the same bytes carry different data (one sort of every write by address),
  * there is no hazard anywhere.  Returns 1 when that holds. */
 static int hazard_free(const xg_span *xfer, int n)
 {
-    uint64_t slo = UINT64_MAX, shi = 0, dlo = UINT64_MAX, dhi = 0;
     int i, m = 0, ok = 1;
-    for (i = 0; i < n; ++i)
-        if (xfer[i].len) {
-            if (xfer[i].src < slo) slo = xfer[i].src;
-            if (xfer[i].src + xfer[i].len > shi) shi = xfer[i].src + xfer[i].len;
-            if (xfer[i].dst < dlo) dlo = xfer[i].dst;
-            if (xfer[i].dst + xfer[i].len > dhi) dhi = xfer[i].dst + xfer[i].len;
-            m++;
-        }
+    if (!hulls_disjoint(xfer, n, &m)) return 0;      /* a read may meet a write: full scan */
     if (!m) return 1;
-    if (slo < dhi && dlo < shi) return 0;            /* a read may meet a write: full scan */
     ivl *w = (ivl *)malloc(sizeof(ivl) * (size_t)m);
     if (!w) return 0;
     for (i = 0, m = 0; i < n; ++i)
@@ -163,4 +172,62 @@ int xg_engine_hazards(const xg_span *xfer, const int *step_begin, int nsteps, in
     free(pend);
     free(tmp);
     return nhaz;
+}
+
+/* ---- rails: no barrier between them, so no ordering between steps at all ----
+ * The solo engine's rails (kernels.h solo_engine_kernel) never wait for each other: while
+ * one rail still loads for step s another may already store for step t > s, and a rail's
+ * own loads run a chunk ahead of its stores.  Flag 0 everywhere (no hazard point) is not
+ * enough for that: write-after-read gets no flag, because the grid engine's barrier orders
+ * it.  A segment may run on rails only if no transfer's source range meets the destination
+ * range of a transfer of ANOTHER step, whichever of the two steps comes first.  (Writes of
+ * the same bytes by several steps are xg_engine_hazards' business: identical ones are
+ * harmless in any order, others are hazard points.) */
+typedef struct {
+    uint64_t lo, hi;      /* destination byte range [lo, hi) */
+    int step;
+} wrt;
+
+static int cmp_wrt(const void *a, const void *b)
+{
+    const wrt *x = (const wrt *)a, *y = (const wrt *)b;
+    return x->lo != y->lo ? (x->lo < y->lo ? -1 : 1) : 0;
+}
+
+int xg_engine_rail_safe(const xg_span *xfer, const int *step_begin, int nsteps)
+{
+    int m = 0, s, k, i, ok = 1;
+    if (nsteps <= 0 || hulls_disjoint(xfer, step_begin[nsteps], &m)) return 1;
+    wrt *w = (wrt *)malloc(sizeof(wrt) * (size_t)m);
+    uint64_t *reach = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)m);   /* max hi of w[0..i] */
+    if (!w || !reach) {
+        free(w);
+        free(reach);
+        return 0;
+    }
+    for (s = 0, m = 0; s < nsteps; ++s)
+        for (k = step_begin[s]; k < step_begin[s + 1]; ++k)
+            if (xfer[k].len) {
+                w[m].lo = xfer[k].dst;
+                w[m].hi = xfer[k].dst + xfer[k].len;
+                w[m].step = s;
+                m++;
+            }
+    qsort(w, (size_t)m, sizeof(wrt), cmp_wrt);
+    for (i = 0; i < m; ++i) reach[i] = i && reach[i - 1] > w[i].hi ? reach[i - 1] : w[i].hi;
+    for (s = 0; s < nsteps && ok; ++s)
+        for (k = step_begin[s]; k < step_begin[s + 1] && ok; ++k) {
+            const uint64_t a = xfer[k].src, b = xfer[k].src + xfer[k].len;
+            int lo = 0, hi = m;
+            if (!xfer[k].len) continue;
+            while (lo < hi) {                          /* writes [0, lo) start below b */
+                const int mid = (lo + hi) >> 1;
+                if (w[mid].lo < b) lo = mid + 1; else hi = mid;
+            }
+            for (i = lo - 1; i >= 0 && reach[i] > a && ok; --i)
+                if (w[i].hi > a && w[i].step != s) ok = 0;
+        }
+    free(w);
+    free(reach);
+    return ok;
 }

@@ -647,10 +647,16 @@ __global__ __launch_bounds__(kThreads) void step_engine_kernel(const DCopy *__re
 // back across steps.  K rows are loaded at once (every lane has K 16-B loads in
 // flight, 16 x K KiB per workgroup) and stored in order, with a barrier + wall-
 // clock stamp wherever a step that had pieces on this rail ends: the loads of
-// later steps run ahead of the stores of earlier ones -- valid because no step
-// reads what another writes (the host uses this engine only for plans without
-// hazard points, xg_engine_hazards) -- while each rail's stores keep the step
-// order.  Rails never wait for each other: step s is over when every rail has
+// later steps run ahead of the stores of earlier ones, and rails never wait for
+// each other, so nothing orders a load of one step against a store of another,
+// earlier or later.  That is valid only because the host takes this engine for a
+// segment when (1) no transfer's source range meets the destination range of a
+// transfer of another step, in either step order (xg_engine_rail_safe -- this
+// covers write-after-read, which xg_engine_hazards does not flag because the
+// grid engine's barrier orders it), and (2) it has no hazard point
+// (xg_engine_hazards: bytes written twice are written with the same data, so the
+// order of those stores across rails does not matter either).  Each rail's own
+// stores keep the step order.  Step s is over when every rail has
 // closed it, so its time is the MAX over rails of their stamps for it (a rail with
 // nothing in step s carries its previous stamp; the host reduces).  Like flag 0 of
 // the grid engine a stamp is the time the stores were issued; the last step waits

@@ -61,6 +61,7 @@ struct SegCand {
     uintptr_t slo, shi, dlo, dhi;
     xg_solo_shape sh;
     bool fits;                     // the solo tables can be built (limits, alignment, window)
+    bool rail_safe;                // no step reads what another writes (xg_engine_rail_safe)
 };
 
 static SegCand seg_candidate(const xg_plan *p, const std::vector<xgk::DCopy> &pieces, int s0, int s1)
@@ -105,6 +106,12 @@ static SegCand seg_candidate(const xg_plan *p, const std::vector<xgk::DCopy> &pi
             k.slo = std::min<uintptr_t>(k.slo, x.src); k.shi = std::max<uintptr_t>(k.shi, x.src + x.len);
             k.dlo = std::min<uintptr_t>(k.dlo, x.dst); k.dhi = std::max<uintptr_t>(k.dhi, x.dst + x.len);
         }
+    // Rails never wait for each other, so a segment runs on them only if no step reads what
+    // another step writes, in either order: a write-after-read gets no hazard flag (the grid
+    // barrier orders it) but races on rails.  Disjoint source and destination hulls (every
+    // SEND -> RECV plan) prove it without a scan.
+    k.rail_safe = k.shi <= k.dlo || k.dhi <= k.slo ||
+                  xg_engine_rail_safe(k.spans.data(), k.tb.data(), k.n) != 0;
     k.fits = (k.gran == 16 || c->solo_waves == 1) && k.shi > k.slo && k.dhi > k.dlo && k.n <= xgk::kSoloMaxSteps &&
              k.bytes <= c->solo_max &&
              xg_solo_tables_g(k.spans.data(), k.tb.data(), k.n, c->solo_rails, c->solo_waves, k.gran, k.slo, k.dlo,
@@ -264,9 +271,9 @@ static int build_segments(xg_plan *p, const std::vector<xgk::DCopy> &pieces)
             continue;
         }
         SegCand k = seg_candidate(p, pieces, s, e);
-        const bool solo = k.nhaz == 0 && k.fits && c->solo &&
+        const bool solo = k.nhaz == 0 && k.rail_safe && k.fits && c->solo &&
                           solo_pays(k.bytes, k.n, k.sh.rails, c->solo_waves, busy, k.gran);
-        if (!solo && k.nhaz == 0 && c->solo && !k.fits && k.n >= 2) {
+        if (!solo && k.nhaz == 0 && k.rail_safe && c->solo && !k.fits && k.n >= 2) {
             // too long for one solo launch (more than kSoloMaxSteps steps -- e.g. a large -k --,
             // more bytes or pieces per rail than one launch holds): consecutive solo launches,
             // each a kernel boundary, when that beats one grid launch's barrier per step
@@ -275,7 +282,7 @@ static int build_segments(xg_plan *p, const std::vector<xgk::DCopy> &pieces)
             bool all = !cut.empty() && cut.size() > 1;
             for (size_t i = 0; all && i < cut.size(); ++i) {
                 parts.push_back(seg_candidate(p, pieces, cut[i].first, cut[i].second));
-                all = parts.back().fits && parts.back().nhaz == 0;
+                all = parts.back().fits && parts.back().nhaz == 0 && parts.back().rail_safe;
             }
             const double traffic = 2.0 * (double)k.bytes;
             const double grid = traffic / 5e12 + k.n * 1.0e-6;

@@ -217,6 +217,7 @@ def host():
         h.xg_verify_slots.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Slot)]
         h.xg_deliveries.argtypes = [C.c_void_p, C.c_int, C.POINTER(Delivery)]
         h.xg_engine_hazards.argtypes = [C.POINTER(Span), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int)]
+        h.xg_engine_rail_safe.argtypes = [C.POINTER(Span), C.POINTER(C.c_int), C.c_int]
         h.xg_solo_reduce_stamps.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int64, C.c_int, C.c_int,
                                             C.POINTER(C.c_uint64)]
         h.xg_solo_reduce_stamps.restype = None
@@ -249,6 +250,18 @@ def engine_hazards(steps, force=False):
     fl = (C.c_int * max(1, len(steps)))()
     n = host().xg_engine_hazards(arr, sb, len(steps), 1 if force else 0, fl)
     return list(fl)[:len(steps)], n
+
+
+def rail_safe(steps):
+    """xg_engine_rail_safe over steps = [[(src, dst, len), ...], ...]: may they run on the solo
+    engine's unsynchronised rails (no source range meets another step's destination range)?"""
+    spans = [x for st in steps for x in st]
+    arr = (Span * max(1, len(spans)))(*[Span(*x) for x in spans])
+    beg = [0]
+    for st in steps:
+        beg.append(beg[-1] + len(st))
+    sb = (C.c_int * len(beg))(*beg)
+    return bool(host().xg_engine_rail_safe(arr, sb, len(steps)))
 
 
 def solo_tables(steps, rails_max, src_base, dst_base, waves=16, granule=16):

@@ -120,6 +120,181 @@ def wave_edge_steps(kib):
     return steps, send_bytes, recv_bytes
 
 
+# ------------------------------------------------------------------ step-engine plans
+# (test_gpu_solo_synth.py; their host side is checked in test_synth_plan.py)
+PIECE, K = 1024, 8                      # kernels.h kSoloPiece, kSoloK
+SBASE, DBASE = 1 << 32, 3 << 32         # stand-in region addresses for the CPU table builder
+
+# the last access of a piece ends inside, at and past a 64-lane instruction (64 x G bytes)
+SOLO_LENS = {
+    16: [16, 32, 1008, 1024, 1040, 2048, 3 * 1024 + 16],
+    4: [4, 60, 64, 68, 252, 256, 260, 1020, 1024, 1028, 2044],
+    1: [1, 15, 17, 63, 64, 65, 127, 128, 129, 1023, 1024, 1025, 2049],
+}
+
+
+def _solo_pays(nbytes, n, rails, waves, busy, gran):
+    """plan_load.hip solo_pays, mirrored only to SIZE plans (10 % kept in hand on the rail side):
+    the rail count a GPU test asserts is the check that the library's model agreed"""
+    traffic = 2.0 * nbytes
+    if waves == 1:
+        solo = traffic / min(rails * 15e9 * gran / 16.0, 6e12 * gran / 16.0) + n * 0.05e-6
+    else:
+        solo = traffic / (rails * 120e9) + n * 0.2e-6
+    grid = traffic / 5e12 + n * 1.0e-6 + (8e-6 if busy < 2 else 0.0)
+    return 1.1 * solo < grid
+
+
+def _pieces(steps):
+    return sum(-(-n // PIECE) for st in steps for (_a, _b, _c, _d, n) in st)
+
+
+def _rails(steps, rails_max, waves):
+    """the rail count xg_solo_tables_g gives (test_solo_tables.py)"""
+    return max(1, min(rails_max, _pieces(steps) // waves))
+
+
+def _segment(steps):
+    """the steps build_segments keeps: those that move nothing are trimmed off both ends"""
+    busy = [i for i, st in enumerate(steps) if st]
+    return steps[busy[0]:busy[-1] + 1]
+
+
+def _sized(build, rails_max, waves, gran):
+    """build(pad) with the fewest extra empty steps at which the cost model takes rails"""
+    for pad in range(0, 1500, 4):
+        steps, send_bytes, recv_bytes = build(pad)
+        seg = _segment(steps)
+        nbytes = sum(n for st in seg for (_a, _b, _c, _d, n) in st)
+        if _solo_pays(nbytes, len(seg), _rails(steps, rails_max, waves), waves, sum(1 for st in seg if st), gran):
+            return steps, send_bytes, recv_bytes
+    raise AssertionError("no rail routing at this size")
+
+
+def _spans(steps):
+    return [[(SBASE + so, DBASE + do, n) for (_sb, so, _db, do, n) in st] for st in steps]
+
+
+def _tables(xg, steps, rails_max, waves, gran):
+    """the segment's solo tables, on the CPU: (shape, per-rail row barrier counts, per-rail real rows)"""
+    sp = _spans(_segment(steps))
+    srcs = [x[0] for st in sp for x in st]
+    dsts = [x[1] for st in sp for x in st]
+    rc, shape, _descs, close, _csteps, rows = xg.solo_tables(sp, rails_max, min(srcs), min(dsts), waves=waves,
+                                                             granule=gran)
+    assert rc == 0, (rc, shape)
+    if waves == 1:                      # wide form: the row word also carries the piece's length
+        close = [[x & 0xFF for x in r] for r in close]
+    return shape, close, rows
+
+
+# (a) copies per step: empty steps at the start, in the middle and at the end, runs of steps
+# with one tiny copy each, steps of 5-40 copies; `pad` more empty steps go into the first gap
+COUNTS_HEAD = [0, 0, 5, 1, 1, 1, 40, 0, 0]
+COUNTS_TAIL = [13, 1, 1, 27, 0, 1, 33, 7, 1, 1, 1, 1, 40, 0, 0]
+# (granule, waves per rail, XG_SOLO_RAILS; 0 = unset)
+GRANULE_CTX = ([(16, 1, r) for r in (1, 7, 0)] + [(16, 16, r) for r in (1, 3, 16)] +
+               [(4, 1, r) for r in (1, 7, 0)] + [(1, 1, r) for r in (1, 7, 0)])
+
+
+def _granule_steps(G, pad=0):
+    """24 + pad steps whose offsets and lengths are all multiples of G and not all of the next
+    coarser granule (lengths G and SOLO_LENS[G][1]; for G < 16 source and destination phases too)"""
+    lens = SOLO_LENS[G]
+    specs, cuts = [], [0]
+    for count in COUNTS_HEAD + [0] * pad + COUNTS_TAIL:
+        for _ in range(count):
+            i = len(specs)
+            n = lens[i % 2] if count == 1 else lens[i % len(lens)]
+            specs.append((n, (G * (i % 7)) % 16, (G * (i % 5)) % 16))
+        cuts.append(len(specs))
+    copies, send_bytes, recv_bytes = _layout(specs)
+    return [copies[a:b] for a, b in zip(cuts, cuts[1:])], send_bytes, recv_bytes
+
+
+# (b) one piece each / (length, pieces)
+SINGLE = [1024, 16, 1008, 32, 1024]
+MULTI = [(1040, 2), (1024, 1), (3 * 1024 + 16, 4), (2048, 2), (16, 1), (1008, 1)]
+
+
+def _row_pieces(rows, waves):
+    """pieces that fill exactly `rows` rows of one rail: on a 16-wave rail the last row partly (full for one row)"""
+    return rows if waves == 1 else 16 * (rows - 1) + (16 if rows == 1 else 5)
+
+
+def _row_steps(npieces, waves, pad=0):
+    """exactly `npieces` solo pieces: a stretch of one-piece steps (17 for 16-wave rails, so that
+    one row of 16 pieces holds the ends of 15 steps), `pad` empty steps, then steps of up to 12
+    (one-wave rails: 3) copies of 1, 2 and 4 pieces"""
+    specs, cuts, left = [], [0], npieces
+    for i in range(min(left, 17 if waves == 16 else 3)):
+        specs.append((SINGLE[i % 5], 0, 0))
+        cuts.append(len(specs))
+        left -= 1
+    cuts += [len(specs)] * pad
+    i = 0
+    while left:
+        for _ in range(12 if waves == 16 else 3):
+            if not left:
+                break
+            n, q = MULTI[i % 6]
+            i += 1
+            if q > left:
+                n, q = SINGLE[i % 5], 1
+            specs.append((n, 0, 0))
+            left -= q
+        cuts.append(len(specs))
+    copies, send_bytes, recv_bytes = _layout(specs)
+    steps = [copies[a:b] for a, b in zip(cuts, cuts[1:])]
+    assert _pieces(steps) == npieces
+    return steps, send_bytes, recv_bytes
+
+
+def _capacity_steps(per_step):
+    """(c) 40 steps of `per_step` copies of 16-48 B, one solo piece each"""
+    cyc = [16, 16, 32, 16, 48]
+    copies, send_bytes, recv_bytes = _layout([(cyc[i % 5], 0, 0) for i in range(40 * per_step)])
+    return [copies[t * per_step:(t + 1) * per_step] for t in range(40)], send_bytes, recv_bytes
+
+
+ROUND_LENS = [16, 4096, 256, 1024, 33, 2048, 4095, 512, 48, 17]           # <= one 4 KiB unit each
+
+
+def _round_steps(nsteps, per, reader):
+    """grid engine: `nsteps` steps of `per` transfers of 16 B - 4 KiB, each its own unit; lengths
+    33, 4095 and 17 and every 7th transfer's phases are off the 16-B grid (the byte path; as a
+    workgroup's first unit of a step it is not prefetched).  reader: step 1 instead reads step
+    0's destinations, RECV -> RECV, into destinations of its own."""
+    specs = []
+    for i in range(nsteps * per):
+        odd = i % 7 == 3
+        specs.append((ROUND_LENS[i % len(ROUND_LENS)], i % 16 if odd else 0, (5 * i) % 16 if odd else 0))
+    copies, send_bytes, recv_bytes = _layout(specs)
+    steps = [copies[t * per:(t + 1) * per] for t in range(nsteps)]
+    if reader:
+        assert per % len(ROUND_LENS) == 0          # copy k of step 1 is as long as copy k of step 0
+        steps[1] = [(1, a[3], 1, b[3], b[4]) for a, b in zip(steps[0], steps[1])]
+        assert all(a[4] == b[4] for a, b in zip(steps[0], steps[1]))
+    return steps, send_bytes, recv_bytes
+
+
+UNIT64 = 64 << 10
+
+
+def _unit64_steps():
+    """grid engine, 64 KiB units: transfers of unit - 16, unit, unit + 16 and 3 * unit + 4080 bytes
+    (a last unit 16 B short of full, exactly full, of 16 B, of 4080 B), 11 such groups in the
+    step above 4 MiB, transfers of a few KiB at odd phases, and a step that moves nothing"""
+    group = [(UNIT64 - 16, 0, 0), (UNIT64, 0, 0), (UNIT64 + 16, 0, 0), (3 * UNIT64 + 4080, 0, 0)]
+    spec_steps = [group + [(3 * 1024 + 5, 3, 9)], 11 * group + [(5 * 1024 + 1, 8, 1), (2 * 1024 + 7, 15, 15)], [], group]
+    copies, send_bytes, recv_bytes = _layout([x for st in spec_steps for x in st])
+    steps, b = [], 0
+    for st in spec_steps:
+        steps.append(copies[b:b + len(st)])
+        b += len(st)
+    return steps, send_bytes, recv_bytes
+
+
 def _ctx_env(xg, **env):
     old = {k: os.environ.get(k) for k in env}
     os.environ.update({k: str(v) for k, v in env.items()})
@@ -179,13 +354,27 @@ class Synth:
                 bufs[db][do:do + ln] = v
         return bufs[1]
 
-    def run(self):
+    def run_timed(self):
+        """one run -> (RECV, step completion times, wall time), seconds from the run's start"""
         n = max(1, len(self.steps))
         done, post, wall = (C.c_double * n)(), (C.c_double * n)(), C.c_double()
         assert self.d.xg_plan_run(self.p, done, post, C.byref(wall)) == 0
         out = C.create_string_buffer(len(self.recv))
         assert self.d.xg_regions_read(self.r, 1, 0, out, len(self.recv)) == 0
-        return np.frombuffer(out.raw, np.uint8)
+        return np.frombuffer(out.raw, np.uint8), list(done)[:len(self.steps)], wall.value
+
+    def run(self):
+        return self.run_timed()[0]
+
+    def poison(self):
+        """RECV back to 0xA5 everywhere (xg_regions_poison)"""
+        assert self.d.xg_regions_poison(self.r) == 0
+
+    def write_recv(self, image):
+        """the whole RECV region := image"""
+        buf = np.ascontiguousarray(image, np.uint8).tobytes()
+        assert len(buf) == len(self.recv)
+        assert self.d.xg_regions_write(self.r, 1, 0, buf, len(buf)) == 0
 
     def close(self):
         self.d.xg_plan_free(self.p)

@@ -39,6 +39,52 @@ def test_write_after_read_needs_no_flag(xg):
     assert flags == [0, 1]
 
 
+def test_write_after_read_is_not_rail_safe(xg):
+    """the same two steps as above: flags [0, 1] and no hazard point, right for the grid engine
+    whose barrier separates them -- but rails never wait for each other, so a rail already in
+    step 1 may overwrite RECV[0..4096) before another has loaded it for step 0"""
+    war = [[(RECV, RECV + 65536, 4096)], [(SEND, RECV, 4096)]]
+    assert xg.engine_hazards(war) == ([0, 1], 0)
+    assert not xg.rail_safe(war)
+    assert not xg.rail_safe(war[::-1])                       # read-after-write: either step order
+    # one byte of overlap on either end is enough; touching ranges are not
+    assert not xg.rail_safe([[(RECV + 4095, RECV + 65536, 4096)], [(SEND, RECV, 4096)]])
+    assert not xg.rail_safe([[(RECV, RECV + 65536, 4096)], [(SEND, RECV + 4095, 4096)]])
+    assert xg.rail_safe([[(RECV + 4096, RECV + 65536, 4096)], [(SEND, RECV, 4096)]])
+    assert xg.rail_safe([[(RECV, RECV + 65536, 4096)], [(SEND, RECV + 4096, 4096)]])
+    # the write found behind a longer one that starts lower, and far from the first step
+    steps = [[(RECV + 100, RECV + (1 << 20), 8)]] + [[(SEND, RECV + (2 << 20) + 64 * i, 64)] for i in range(40)]
+    assert xg.rail_safe(steps)
+    assert not xg.rail_safe(steps + [[(SEND, RECV, 4096), (SEND + 8192, RECV + 50, 10)]])
+    # a read and a write of the SAME step are the step's own business (simultaneous copies)
+    assert xg.rail_safe([[(RECV, RECV + 65536, 4096), (SEND, RECV, 4096)]])
+    assert xg.rail_safe([[(RECV, RECV + 8192, 0)], [(SEND, RECV, 4096)]])     # empty transfers are ignored
+    assert xg.rail_safe([[], []]) and xg.rail_safe([])
+
+
+def test_identical_rewrites_are_rail_safe(xg):
+    s = [(SEND, RECV, 4096)]
+    assert xg.rail_safe([s, s, s])
+    # SEND -> RECV with other bytes: a hazard point (xg_engine_hazards' business), no read meets a write
+    assert xg.rail_safe([[(SEND, RECV, 4096)], [(SEND + 4096, RECV + 2048, 4096)]])
+
+
+def test_rail_safe_matches_a_direct_walk(xg):
+    """random step lists inside one small region against the definition, pair by pair"""
+    import random
+    rng = random.Random(7)
+    seen = set()
+    for _ in range(300):
+        steps = [[(RECV + rng.randrange(0, 600), RECV + rng.randrange(0, 600), rng.choice([0, 1, 7, 40, 90]))
+                  for _k in range(rng.randint(0, 3))] for _s in range(rng.randint(1, 5))]
+        want = not any(ls and ld and s < d + ld and d < s + ls
+                       for a, sa in enumerate(steps) for b, sb in enumerate(steps) if a != b
+                       for (s, _d, ls) in sa for (_s, d, ld) in sb)
+        assert xg.rail_safe(steps) == want, steps
+        seen.add(want)
+    assert seen == {True, False}
+
+
 def test_hazard_point_clears_pending_writes(xg):
     a = [(SEND, RECV, 4096)]
     b = [(RECV, RECV + 8192, 4096)]          # reads a's output: hazard after step 0
@@ -77,6 +123,11 @@ def test_real_plans_have_no_hazards(xg, method, k):
     base = {b: (b + 1) << 40 for b in range(xg.NBUF)}
     flags, n = xg.engine_hazards(_spans(v, base))
     assert n == 0 and flags[-1] == 1 and all(f == 0 for f in flags[:-1]), (method, k, flags)
+    # ... and no step reads what another writes: they may run on the solo engine's rails
+    assert xg.rail_safe(_spans(v, base)), (method, k)
+    # the same by the full scan: one more copy, from above every region to below them, makes the
+    # source and destination hulls overlap and meets nothing
+    assert xg.rail_safe(_spans(v, base) + [[(1 << 50, 4096, 16)]]), (method, k)
 
 
 @pytest.mark.parametrize("method", [15, 16])
