@@ -167,7 +167,12 @@ int xg_plan_engine_rails(const xg_plan *p);
 int xg_plan_engine_steps(const xg_plan *p, int *nseg, int *nhaz);
 /* Kernel launches of one run (copy + engine launches; RCCL's own kernels aside). */
 int xg_plan_launches(const xg_plan *p);
-/* Of those, the copy launches that run the wave-persistent copy_kernel_w.  *grid = the context's
+/* The copy launches of one run -- entries of the launch table: one of several dispatches counts
+ * once -- whose kernel is of `kind` (XG_COPY_PIECE .. XG_COPY_SMALL, xg_sched.h: every launch has
+ * exactly one, chosen at load by xg_copy_launch_choose).  The four counters below are this one for
+ * WAVE, SHIFT, EXTENT and SMALL, with their outputs. */
+int xg_plan_kind_launches(const xg_plan *p, int kind);
+/* The copy launches that run the wave-persistent copy_kernel_w.  *grid = the context's
  * cap on its workgroups (occupancy x CUs; XG_WAVE_GRID, a test hook, lowers it);
  * *max_pieces_per_wave = the largest ceil(pieces / (4 x workgroups)) over those launches, a
  * launch of n pieces starting min(grid, ceil(n / 4)) workgroups of 4 waves.  Either may be NULL. */

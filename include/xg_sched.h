@@ -426,6 +426,61 @@ inline XG_HD xg_small_at xg_small_index(uint32_t b, uint32_t copies, int64_t len
 int xg_small_piece_at(int64_t b, int64_t copies, int64_t len, int64_t piece, int k, int64_t *copy, int64_t *off,
                       int64_t *n);
 
+/* The kernel of one copy launch (pieces.c).  A launch of bytes > 0 runs exactly one KIND, chosen
+ * once at plan load from what the launch is (facts) and the context's knobs (rules), by this
+ * precedence:
+ *   1. EXTENT (copy_kernel_x): a placement plan (XG_DP_EXTENTS), extent_copy on, chunk <= 16 MiB,
+ *      bytes <= npos * extent_mean_max (short copies).  Pieces by xg_piece_size.
+ *   2. WAVE (copy_kernel_w<kib>): cross, wave_min <= bytes <= wave_max, everything 16-B aligned, the
+ *      cut plain (!nt_cut).  Pieces of kib KiB: wave_kib if forced, else by bytes and cus (8 / 4 /
+ *      2).  When the run is non-temporal all the same (nt_run; they differ in one launch, the local +
+ *      pack launch of a step whose packs are all empty) the kind is PIECE over those wave-sized pieces.
+ *   3. SHIFT (copy_kernel_s): a ragged plan (XG_DP_RAGGED), ragged_copy on, an offset or length off
+ *      the 16-B grid.  Pieces by xg_piece_size.
+ *   4. PIECE (copy_kernel_g<4>) otherwise.  Pieces by xg_piece_size.
+ *   5. SMALL (copy_kernel_q<kib / 4>) replaces PIECE only: may_small, small_pieces on, aligned,
+ *      bytes >= small_piece_min, uniform_len > 0, and npos * ppc and small_order * ppc within
+ *      INT32_MAX (ppc = pieces per copy; xg_small_index works in 32 bits).  kib = small_kib, order =
+ *      small_order; the launch has rows, no pieces.
+ * nt is nt_run in every case (WAVE is reached only with a plain run). */
+enum { XG_COPY_PIECE = 0, XG_COPY_WAVE, XG_COPY_SHIFT, XG_COPY_EXTENT, XG_COPY_SMALL, XG_COPY_NKIND };
+typedef struct {
+    int64_t bytes, npos;        /* over the positive copies: their bytes, their number ...            */
+    uint64_t bits;              /* ... the OR of their offsets and lengths (the alignment bits) ...    */
+    int64_t uniform_len;        /* ... and their common length; -1 once two differ or one packs or     */
+                                /* unpacks (dst STAGE_SEND / src STAGE_RECV); 0 before the first       */
+    const int64_t *lens;        /* every copy's length, for xg_piece_size                              */
+    int32_t nlens;
+    int32_t dp_flags;           /* the plan's XG_DP_*                                                  */
+    int32_t cross;              /* a launch of a cross-GPU step, or of a local step too large for the engine */
+    int32_t may_small;          /* a step's own local (+ pack) launch                                  */
+    int32_t nt_cut, nt_run;     /* non-temporal by the runtime's copy_variant: for the cut, for the kernel */
+} xg_launch_facts;
+typedef struct {
+    int64_t chunk;              /* default bytes per piece (xg_set_copy_params)                        */
+    int64_t wave_min, wave_max; /* WAVE from .. to this many bytes (XG_COPY_WAVE_MIN; kWaveMax)        */
+    int64_t wg_cost;            /* xg_piece_size's per-workgroup start (kWgCost)                       */
+    int64_t extent_mean_max;    /* EXTENT up to this mean positive length (kExtMeanMax)                */
+    int64_t small_piece_min;    /* SMALL from this many bytes (kSmallMin; XG_SMALL_PIECE_MIN)          */
+    int32_t cus;                /* compute units                                                       */
+    int32_t wave_kib;           /* XG_WAVE_KIB: 2 / 4 / 8 forced, 0 = by launch bytes                  */
+    int32_t ragged_copy;        /* 0 (XG_RAGGED_COPY=0): no SHIFT                                      */
+    int32_t extent_copy;        /* 0 (XG_EXTENT_COPY=0): no EXTENT                                     */
+    int32_t small_pieces;       /* 0 (XG_SMALL_PIECES=0): no SMALL                                     */
+    int32_t small_kib;          /* SMALL's piece size, 4 or 8 KiB (kSmallKiB; XG_SMALL_PIECE_KIB)      */
+    int32_t small_order;        /* copies per group of its piece order (xg_small_index's k)            */
+} xg_copy_rules;
+typedef struct {
+    int32_t kind, nt;
+    int32_t kib;                /* WAVE: 2 / 4 / 8; SMALL: 4 / 8; else 0                               */
+    int32_t order;              /* SMALL: xg_small_index's k; else 0                                   */
+    int64_t piece;              /* bytes per piece the launch's copies are cut to (SMALL: by the kernel) */
+} xg_copy_choice;
+/* one copy of the launch into zeroed facts (lens / nlens and the six fields below them are the caller's) */
+void xg_launch_facts_add(xg_launch_facts *f, const xg_copy *c);
+/* 0, or -1 for a NULL argument or a launch without bytes (it has no kernel) */
+int xg_copy_launch_choose(const xg_launch_facts *f, const xg_copy_rules *r, xg_copy_choice *out);
+
 /* ---------------------------------------------------------------- placement (place.c)
  * Where the segments of an exchange lie in the aggregators' collective buffers (ROMIO's
  * others_req[i].offsets / lens): a list of n extents describes the whole job, and every rank

@@ -1,7 +1,7 @@
 /*
- * pieces.c -- how copy launches are formed (host side of the copy kernel): how a launch is
- * cut into workgroup pieces, and whether a step's local copies may share a launch with the
- * previous step's unpacks.
+ * pieces.c -- how copy launches are formed (host side of the copy kernels): which kernel kind a
+ * launch runs and how it is cut into workgroup pieces (xg_copy_launch_choose), and whether a
+ * step's local copies may share a launch with the previous step's unpacks.
  *
  * One workgroup copies one piece.  A launch of w pieces puts ceil(w / CUs) of them on its
  * busiest CU, and the launch lasts about as long as that CU works: pieces x (piece bytes + a
@@ -84,6 +84,72 @@ int xg_small_piece_at(int64_t b, int64_t copies, int64_t len, int64_t piece, int
     return 0;
 }
 
+void xg_launch_facts_add(xg_launch_facts *f, const xg_copy *c)
+{
+    if (c->len <= 0) return;
+    f->bytes += c->len;
+    f->npos++;
+    f->bits |= (uint64_t)c->src_off | (uint64_t)c->dst_off | (uint64_t)c->len;
+    /* a pack's or unpack's staging side is patched per piece by the device scan: never a row */
+    if (c->dst_buf == XG_BUF_STAGE_SEND || c->src_buf == XG_BUF_STAGE_RECV ||
+        (f->uniform_len && f->uniform_len != c->len))
+        f->uniform_len = -1;
+    else
+        f->uniform_len = c->len;
+}
+
+/* Piece KiB of a copy_kernel_w launch of `bytes`: the largest of 8 / 4 / 2 that still gives every
+ * CU a 4-wave workgroup (bytes / piece >= 4 x CUs): a 4 MiB launch in 8 KiB pieces is 512 waves =
+ * 128 workgroups, half the chip (the local part of a configs[2] step, profiles/r05/share_launches/);
+ * in 4 KiB pieces it is 256 workgroups.  Smaller launches take 2 KiB pieces. */
+static int wave_kib_for(int64_t bytes, int cus)
+{
+    int kib;
+    for (kib = 8; kib > 2; kib /= 2)
+        if (bytes / ((int64_t)kib << 10) >= 4 * (int64_t)cus) return kib;
+    return 2;
+}
+
+/* The precedence, top to bottom: EXTENT, WAVE (whose pieces a non-temporal run copies as PIECE),
+ * SHIFT, PIECE -- and SMALL in place of PIECE only (xg_sched.h says when each applies). */
+int xg_copy_launch_choose(const xg_launch_facts *f, const xg_copy_rules *r, xg_copy_choice *out)
+{
+    int aligned;
+    int64_t small, ppc;
+    if (!f || !r || !out || f->bytes <= 0 || f->npos <= 0) return -1;
+    aligned = (f->bits & 15) == 0;
+    out->kind = XG_COPY_PIECE;
+    out->nt = f->nt_run != 0;
+    out->kib = out->order = 0;
+    out->piece = 0;
+    if ((f->dp_flags & XG_DP_EXTENTS) && r->extent_copy && r->chunk <= (1 << 24) &&
+        f->bytes <= f->npos * r->extent_mean_max) {
+        out->kind = XG_COPY_EXTENT;
+    } else if (f->cross && f->bytes >= r->wave_min && f->bytes <= r->wave_max && aligned && !f->nt_cut) {
+        const int kib = r->wave_kib ? r->wave_kib : wave_kib_for(f->bytes, r->cus);
+        out->piece = (int64_t)kib << 10;
+        if (!f->nt_run) {       /* else: the cut says plain, the kernel non-temporal -- PIECE over wave-sized pieces */
+            out->kind = XG_COPY_WAVE;
+            out->kib = kib;
+        }
+    } else if ((f->dp_flags & XG_DP_RAGGED) && r->ragged_copy && !aligned) {
+        out->kind = XG_COPY_SHIFT;
+    }
+    if (!out->piece) out->piece = xg_piece_size(f->lens, f->nlens, r->chunk, r->cus, r->wg_cost);
+    if (out->kind != XG_COPY_PIECE || !f->may_small || !r->small_pieces || !aligned ||
+        f->bytes < r->small_piece_min || f->uniform_len <= 0 || r->small_kib < 1)
+        return 0;
+    small = (int64_t)r->small_kib << 10;
+    ppc = (f->uniform_len + small - 1) / small;
+    /* xg_small_index works in 32 bits: the launch's workgroups and a group's */
+    if (f->npos * ppc > INT32_MAX || r->small_order * ppc > INT32_MAX) return 0;
+    out->kind = XG_COPY_SMALL;
+    out->kib = r->small_kib;
+    out->order = r->small_order;
+    out->piece = small;
+    return 0;
+}
+
 /* [off, end) of region buf */
 typedef struct { int64_t lo, hi; } ival;
 
@@ -91,60 +157,6 @@ static int ival_cmp(const void *x, const void *y)
 {
     const ival *a = (const ival *)x, *b = (const ival *)y;
     return a->lo < b->lo ? -1 : a->lo > b->lo;
-}
-
-/* Step s's local copies (after its stage copies, before its packs) against the bytes step
- * s-1's unpacks write: 1 if any of them reads or writes such a byte -- then they cannot share
- * one launch, whose workgroups run in any order (runtime/plan_load.hip fuses them otherwise).
- * Returns -1 for a bad step. */
-int xg_step_local_meets_unpacks(const xg_devplan *dp, int s)
-{
-    const xg_stepplan *pv, *sp;
-    ival *w[XG_NBUF] = {0};
-    int64_t *reach[XG_NBUF] = {0};
-    int nw[XG_NBUF] = {0}, i, k, hit = 0;
-    if (!dp || s < 1 || s >= dp->nsteps) return -1;
-    pv = &dp->steps[s - 1];
-    sp = &dp->steps[s];
-    for (k = 0; k < XG_NBUF; ++k) {
-        w[k] = (ival *)malloc(sizeof(ival) * ((size_t)pv->post_count + 1));
-        reach[k] = (int64_t *)malloc(sizeof(int64_t) * ((size_t)pv->post_count + 1));
-        if (!w[k] || !reach[k]) { hit = 1; goto done; }   /* refuse the fusion when in doubt */
-    }
-    for (i = 0; i < pv->post_count; ++i) {
-        const xg_copy *c = &dp->copies[pv->post_begin + i];
-        if (c->len > 0 && c->dst_buf >= 0 && c->dst_buf < XG_NBUF) {
-            w[c->dst_buf][nw[c->dst_buf]].lo = c->dst_off;
-            w[c->dst_buf][nw[c->dst_buf]++].hi = c->dst_off + c->len;
-        }
-    }
-    for (k = 0; k < XG_NBUF; ++k) {
-        int64_t m = INT64_MIN;
-        qsort(w[k], nw[k], sizeof(ival), ival_cmp);
-        for (i = 0; i < nw[k]; ++i) reach[k][i] = m = w[k][i].hi > m ? w[k][i].hi : m;
-    }
-    for (i = sp->stage_count; i < sp->pre_count && !hit; ++i) {
-        const xg_copy *c = &dp->copies[sp->pre_begin + i];
-        int side;
-        if (c->dst_buf == XG_BUF_STAGE_SEND) break;          /* the packs start */
-        if (c->len <= 0) continue;
-        for (side = 0; side < 2 && !hit; ++side) {
-            const int buf = side ? c->dst_buf : c->src_buf;
-            const int64_t a = side ? c->dst_off : c->src_off, b = a + c->len;
-            int lo = 0, hi;
-            if (buf < 0 || buf >= XG_NBUF) continue;
-            hi = nw[buf];                                    /* intervals starting before b: [0, lo) */
-            while (lo < hi) {
-                const int mid = (lo + hi) / 2;
-                if (w[buf][mid].lo < b) lo = mid + 1;
-                else hi = mid;
-            }
-            hit = lo > 0 && reach[buf][lo - 1] > a;
-        }
-    }
-done:
-    for (k = 0; k < XG_NBUF; ++k) { free(w[k]); free(reach[k]); }
-    return hit;
 }
 
 /* sorted intervals of one kind (reads or writes) of a set of copies, per region, with running
@@ -196,6 +208,30 @@ static void ivset_free(ivset *t)
 {
     int k;
     for (k = 0; k < XG_NBUF; ++k) { free(t->v[k]); free(t->reach[k]); }
+}
+
+/* Step s's local copies (after its stage copies, before its packs) against the bytes step
+ * s-1's unpacks write: 1 if any of them reads or writes such a byte -- then they cannot share
+ * one launch, whose workgroups run in any order (runtime/plan_load.hip fuses them otherwise).
+ * Returns -1 for a bad step. */
+int xg_step_local_meets_unpacks(const xg_devplan *dp, int s)
+{
+    const xg_stepplan *pv, *sp;
+    ivset w = {{0}, {0}, {0}};
+    int i, hit;
+    if (!dp || s < 1 || s >= dp->nsteps) return -1;
+    pv = &dp->steps[s - 1];
+    sp = &dp->steps[s];
+    hit = ivset_build(&w, dp->copies + pv->post_begin, pv->post_count, 1) != 0;   /* refuse the fusion when in doubt */
+    for (i = sp->stage_count; i < sp->pre_count && !hit; ++i) {
+        const xg_copy *c = &dp->copies[sp->pre_begin + i];
+        if (c->dst_buf == XG_BUF_STAGE_SEND) break;          /* the packs start */
+        if (c->len <= 0) continue;
+        hit = ivset_meets(&w, c->src_buf, c->src_off, c->src_off + c->len) ||
+              ivset_meets(&w, c->dst_buf, c->dst_off, c->dst_off + c->len);
+    }
+    ivset_free(&w);
+    return hit;
 }
 
 /* Step s's stage copies (TAM rank-local memcpy's through SCRATCH) against its other pre copies

@@ -11,11 +11,13 @@
 //  fill_kernel        fill_buffer / MAP_DATA (mpi_test.c:71-77, :23): byte o of a
 //                     segment of `rank` with seed `seed` = (rank + o + seed + iter)
 //                     mod 256, produced 16 bytes per lane with SWAR byte adds.
-//  copy_kernel_g / _b the exchange itself: one workgroup per <= chunk-byte piece of
+//  copy_kernel_g      the exchange itself: one workgroup per <= chunk-byte piece of
 //                     a segment transfer (local gather/scatter, pack into and unpack
 //                     out of RCCL staging).  Replaces the shared-memory copies MPI
 //                     does inside Irecv/Issend/Alltoallw.  Misaligned pieces (-d not
 //                     a multiple of 16) are realigned through LDS.
+//  copy_kernel_w      the same over pieces of 2 / 4 / 8 KiB, one per WAVE, on a persistent grid: the
+//                     aligned plain launches of 1 - 32 MiB of cross-GPU steps.
 //  copy_kernel_q      a large uniform launch in 4 / 8 KiB pieces: one table row per copy, the piece
 //                     found by index arithmetic, straight-line buffer loads then stores.
 //  copy_kernel_s      the copy of a ragged exchange: one workgroup per piece at any source

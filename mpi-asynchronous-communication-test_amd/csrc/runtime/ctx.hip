@@ -190,38 +190,41 @@ static int init_ctx(xg_ctx *c, const void *uid)
     warn_folded_knobs();
     const int device = c->device, rank = c->rank, nranks = c->nranks;
     (void)rank;
-    c->chunk = 32768; c->variant = 0; c->kt_mode = 0; c->nk = 0; c->kt_bytes = 0;   // profiles/r01_copy_ab.txt
+    // c->rules: the knobs of xg_copy_launch_choose (xg_sched.h), from rt.h's constants and the environment
+    c->rules.chunk = 32768; c->variant = 0; c->kt_mode = 0; c->nk = 0; c->kt_bytes = 0;   // profiles/r01_copy_ab.txt
+    c->rules.wg_cost = kWgCost;
+    c->rules.wave_max = kWaveMax;
     const char *env = getenv("XG_COPY_VARIANT");          // 0 by size (default), 1 plain, 6 non-temporal
     if (env && (atoi(env) == 1 || atoi(env) == 6)) c->variant = atoi(env);
     else if (env && atoi(env) != 0) fprintf(stderr, "xg: XG_COPY_VARIANT=%s ignored (0, 1 or 6)\n", env);
     env = getenv("XG_RAGGED_COPY");          // "0": a ragged plan's misaligned launches stay on copy_kernel_g (A/B)
-    c->ragged_copy = !(env && atoi(env) == 0);
-    // copy_kernel_x for a placement plan's launches of short extents (TableBuilder::open): "0" keeps
+    c->rules.ragged_copy = !(env && atoi(env) == 0);
+    // copy_kernel_x for a placement plan's launches of short extents (xg_copy_launch_choose): "0" keeps
     // them on copy_kernel_s.  XG_EXTENT_MEAN_MAX / XG_EXTENT_TILE_KIB: the routing threshold and the
     // tile's byte cap, for the A/B of profiles/extent_copy_ab.py
     env = getenv("XG_EXTENT_COPY");
-    c->extent_copy = env ? atoi(env) != 0 : kExtDefault;
-    c->extent_mean_max = kExtMeanMax;
+    c->rules.extent_copy = env ? atoi(env) != 0 : kExtDefault;
+    c->rules.extent_mean_max = kExtMeanMax;
     env = getenv("XG_EXTENT_MEAN_MAX");
-    if (env && atol(env) > 0) c->extent_mean_max = atol(env);
+    if (env && atol(env) > 0) c->rules.extent_mean_max = atol(env);
     c->extent_tile = kExtTileBytes;
     env = getenv("XG_EXTENT_TILE_KIB");
     if (env && atoi(env) > 0 && atoi(env) <= 1024) c->extent_tile = (int64_t)atoi(env) << 10;
-    // copy_kernel_q for large uniform launches (TableBuilder::open): "0" restores copy_kernel_g's
+    // copy_kernel_q for large uniform launches (xg_copy_launch_choose): "0" restores copy_kernel_g's
     // 32 KiB pieces.  XG_SMALL_PIECE_MIN: test hook, the launch size it starts at;
     // XG_SMALL_PIECE_KIB (4 / 8) and XG_SMALL_PIECE_ORDER (copies per group of the piece order):
     // for the A/B of profiles/small_pieces_ab.sh
     env = getenv("XG_SMALL_PIECES");
-    c->small_pieces = env ? atoi(env) != 0 : kSmallDefault;
-    c->small_piece_min = kSmallMin;
+    c->rules.small_pieces = env ? atoi(env) != 0 : kSmallDefault;
+    c->rules.small_piece_min = kSmallMin;
     env = getenv("XG_SMALL_PIECE_MIN");
-    if (env && atoll(env) >= 0) c->small_piece_min = atoll(env);
-    c->small_kib = kSmallKiB;
+    if (env && atoll(env) >= 0) c->rules.small_piece_min = atoll(env);
+    c->rules.small_kib = kSmallKiB;
     env = getenv("XG_SMALL_PIECE_KIB");
-    if (env && (atoi(env) == 4 || atoi(env) == 8)) c->small_kib = atoi(env);
-    c->small_order = kSmallOrder;
+    if (env && (atoi(env) == 4 || atoi(env) == 8)) c->rules.small_kib = atoi(env);
+    c->rules.small_order = kSmallOrder;
     env = getenv("XG_SMALL_PIECE_ORDER");
-    if (env && atoi(env) >= 1 && atoi(env) <= 1024) c->small_order = atoi(env);
+    if (env && atoi(env) >= 1 && atoi(env) <= 1024) c->rules.small_order = atoi(env);
     c->engine_max_step = 16 << 20;    // crossover vs one launch per step: profiles/r01_engine_sweep.txt
     env = getenv("XG_ENGINE_MAX_STEP");      // 0: never use the step engine
     if (env) c->engine_max_step = atol(env);
@@ -258,25 +261,25 @@ static int init_ctx(xg_ctx *c, const void *uid)
     {
         int cus = 0;
         HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-        c->cus = cus > 0 ? cus : 256;
+        c->rules.cus = cus > 0 ? cus : 256;
         // the wave-persistent copy for the launches of cross-GPU steps (packs, unpacks, the
         // local part): profiles/r03/wave_copy/ -- one GPU's configs[2] pack launch 5.8 ->
         // 6.25 TB/s; the 448 MiB non-temporal launches stay copy_kernel_g (6.0 vs 5.5-5.8);
         // above kWaveMax the one-piece-per-workgroup launch is as fast or faster
         // (profiles/r03/wave_local/: 28 MiB 9.3 vs 9.9 us, 56 MiB 18.7 vs 18.2, 112 MiB equal)
         env = getenv("XG_COPY_WAVE_MIN");     // test hook: 0 puts every cross-GPU launch on the wave copy
-        c->wave_min = env ? atoll(env) : (int64_t)1 << 20;
+        c->rules.wave_min = env ? atoll(env) : (int64_t)1 << 20;
         int per_cu = 0;
         HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xgk::copy_kernel_w<xgk::kWaveKiB>, xgk::kThreads,
                                                             0));
-        c->wave_grid = c->cus * (per_cu < 1 ? 1 : per_cu);
+        c->wave_grid = c->rules.cus * (per_cu < 1 ? 1 : per_cu);
         // test hook: a positive value caps the grid (never raises it), so that a wave gets several
         // pieces -- on a whole device every launch of <= kWaveMax bytes has one piece per wave
         env = getenv("XG_WAVE_GRID");
         if (env && atoi(env) > 0) c->wave_grid = std::max(1, std::min(c->wave_grid, atoi(env)));
-        // piece KiB of a wave-copy launch: 0 = by its bytes (wave_kib_for), 2 / 4 / 8 forced (A/B)
+        // piece KiB of a wave-copy launch: 0 = by its bytes (pieces.c), 2 / 4 / 8 forced (A/B)
         env = getenv("XG_WAVE_KIB");
-        c->wave_kib = env && (atoi(env) == 2 || atoi(env) == 4 || atoi(env) == 8) ? atoi(env) : 0;
+        c->rules.wave_kib = env && (atoi(env) == 2 || atoi(env) == 4 || atoi(env) == 8) ? atoi(env) : 0;
     }
     env = getenv("XG_STEP_CHAIN");           // "0": a step mark after every step launch
     c->step_chain = !(env && !strcmp(env, "0"));
@@ -434,7 +437,7 @@ extern "C" int xg_device_info(xg_ctx *c, char *name, size_t namelen, int *cus, s
 extern "C" int xg_set_copy_params(xg_ctx *c, int64_t chunk, int variant)
 {
     if (variant > 0 && variant != 1 && variant != 6) return XG_EARG;   // 0 by size, 1 plain, 6 non-temporal
-    if (chunk >= 4096) c->chunk = chunk & ~(int64_t)15;
+    if (chunk >= 4096) c->rules.chunk = chunk & ~(int64_t)15;
     if (variant >= 0) c->variant = variant;
     return XG_OK;
 }

@@ -42,43 +42,59 @@ double mark_elapsed(const xg_plan *p, int i, const std::vector<unsigned long lon
     return (double)(gs[i + 1] - gs[0]) / p->ctx->wall_hz;
 }
 
-// Copy launches.  What a launch is -- its pieces, its kernel (copy_kernel_w<2 / 4 / 8> over
-// wave-sized pieces, copy_kernel_g<4> plain or non-temporal), its dispatches, its stream, the
-// mark behind it -- was decided when the plan was loaded (CopyLaunch, plan_load.hip); here the
-// table is walked.
+// Copy launches.  What a launch is -- its pieces, its ONE kernel kind (PIECE copy_kernel_g<4>,
+// WAVE copy_kernel_w<2 / 4 / 8>, SHIFT copy_kernel_s, EXTENT copy_kernel_x, SMALL copy_kernel_q<1 /
+// 2>; all but WAVE plain or non-temporal), its dispatches, its stream, the mark behind it -- was
+// decided when the plan was loaded (CopyLaunch, plan_load.hip); here the table is walked.
 
 // workgroups (4 waves each) of a copy_kernel_w dispatch over n pieces
 static int wave_wgs(const xg_plan *p, int n) { return std::max(1, std::min(p->ctx->wave_grid, (n + 3) / 4)); }
 
-// One dispatch of launch l: pieces [b, b + n).  Only a launch's first dispatch runs
-// copy_kernel_w; the later ones of a cut wave launch copy their pieces with copy_kernel_g<4>.
+// One dispatch of launch l: pieces [b, b + n) (SMALL: workgroups [b, b + n)), on the kernel of its
+// kind.  The one exception: only the first dispatch of a cut WAVE launch runs copy_kernel_w; the
+// later ones copy their pieces with copy_kernel_g<4>.
 static int launch_one(xg_plan *p, const CopyLaunch &l, int b, int n, hipStream_t st, unsigned long long *start)
 {
     const xgk::DCopy *pc = p->d_pieces + b;
-    if (l.q) {
-        // workgroups [b, b + n) of the launch, each finding its piece of the launch's rows
-        const auto k = l.q == 1 ? (l.nt ? xgk::copy_kernel_q<1, true> : xgk::copy_kernel_q<1, false>)
-                                : (l.nt ? xgk::copy_kernel_q<2, true> : xgk::copy_kernel_q<2, false>);
+    switch (l.kind) {
+    case XG_COPY_SMALL: {
+        // each workgroup finds its piece of the launch's rows
+        const auto k = l.kib == 4 ? (l.nt ? xgk::copy_kernel_q<1, true> : xgk::copy_kernel_q<1, false>)
+                                  : (l.nt ? xgk::copy_kernel_q<2, true> : xgk::copy_kernel_q<2, false>);
         hipLaunchKernelGGL(k, dim3(n), dim3(xgk::kThreads), 0, st, p->d_rows + l.q_row, (uint32_t)b,
                            (uint32_t)l.q_copies, l.q_len, (uint32_t)l.q_k, start);
-    } else if (l.kib && b == l.b) {
-        const auto k = l.kib == 2   ? xgk::copy_kernel_w<2>
-                       : l.kib == 4 ? xgk::copy_kernel_w<4>
-                                    : xgk::copy_kernel_w<xgk::kWaveKiB>;
-        hipLaunchKernelGGL(k, dim3(wave_wgs(p, n)), dim3(xgk::kThreads), 0, st, pc, n, start);
-    } else if (l.ext) {
+        break;
+    }
+    case XG_COPY_EXTENT: {
         // one workgroup per tile of the dispatch (which one: by its first piece)
         int k = 0;
         while (k + 1 < l.ndisp && p->cuts[l.cut + k + 1] <= b) ++k;
         const auto kx = l.nt ? xgk::copy_kernel_x<true> : xgk::copy_kernel_x<false>;
         hipLaunchKernelGGL(kx, dim3(p->xt_n[l.xt + k]), dim3(xgk::kThreads), 0, st, pc, p->d_xt + p->xt_off[l.xt + k],
                            start);
-    } else if (l.shift) {
+        break;
+    }
+    case XG_COPY_SHIFT: {
         const auto k = l.nt ? xgk::copy_kernel_s<true> : xgk::copy_kernel_s<false>;
         hipLaunchKernelGGL(k, dim3(n), dim3(xgk::kThreads), 0, st, pc, start);
-    } else {
+        break;
+    }
+    case XG_COPY_WAVE:
+        if (b == l.b) {
+            const auto k = l.kib == 2   ? xgk::copy_kernel_w<2>
+                           : l.kib == 4 ? xgk::copy_kernel_w<4>
+                                        : xgk::copy_kernel_w<xgk::kWaveKiB>;
+            hipLaunchKernelGGL(k, dim3(wave_wgs(p, n)), dim3(xgk::kThreads), 0, st, pc, n, start);
+            break;
+        }
+        [[fallthrough]];        // a later dispatch (nt is false)
+    case XG_COPY_PIECE: {
         const auto k = l.nt ? xgk::copy_kernel_g<4, true> : xgk::copy_kernel_g<4>;
         hipLaunchKernelGGL(k, dim3(n), dim3(xgk::kThreads), 0, st, pc, start);
+        break;
+    }
+    default:
+        return XG_EARG;
     }
     HIPCHK(hipGetLastError());
     return XG_OK;
@@ -109,11 +125,12 @@ static int kt_after(xg_ctx *c, hipStream_t stream, bool kt, int64_t bytes)
 // session is on.  start: the first dispatch stamps its start there (see copy_kernel_g).
 static int launch_copy(xg_plan *p, const CopyLaunch &l, hipStream_t st, unsigned long long *start)
 {
-    if (start && !l.stamps) return XG_EARG;
     const int *cut = p->cuts.data() + l.cut;
     int rc;
     for (int k = 0; k < l.ndisp; ++k) {
-        const int64_t nb = l.q ? p->qbytes[l.q_bytes + k] : l.ndisp == 1 ? l.bytes : p->plen[cut[k + 1]] - p->plen[cut[k]];
+        const int64_t nb = l.kind == XG_COPY_SMALL ? p->qbytes[l.q_bytes + k]
+                           : l.ndisp == 1          ? l.bytes
+                                                   : p->plen[cut[k + 1]] - p->plen[cut[k]];
         bool kt;
         if ((rc = kt_before(p->ctx, st, &kt))) return rc;
         if ((rc = launch_one(p, l, cut[k], cut[k + 1] - cut[k], st, k == 0 ? start : nullptr))) return rc;
@@ -158,50 +175,41 @@ int enqueue_post(xg_plan *p, int s, hipStream_t stream)
     return XG_OK;
 }
 
-// The dispatches of one run that go to copy_kernel_w, and the geometry launch_one gives them:
-// w workgroups of 4 waves over n pieces.
+// The launch-table entries one run issues (a launch of several dispatches counts once) of one
+// kind, XG_COPY_PIECE .. XG_COPY_SMALL.
+extern "C" int xg_plan_kind_launches(const xg_plan *p, int kind)
+{
+    int count = 0;
+    each_launch(p, [&](const CopyLaunch &l) { count += l.kind == kind; });
+    return count;
+}
+
+// The WAVE launches and the geometry launch_one gives their copy_kernel_w dispatch: w workgroups
+// of 4 waves over n pieces.
 extern "C" int xg_plan_wave_launches(const xg_plan *p, int *grid, int *max_pieces_per_wave)
 {
-    int count = 0, most = 0;
+    int most = 0;
     each_launch(p, [&](const CopyLaunch &l) {
-        if (!l.kib) return;
+        if (l.kind != XG_COPY_WAVE) return;
         const int m = p->cuts[l.cut + 1] - l.b, w = wave_wgs(p, m);
-        ++count;
         most = std::max(most, (m + 4 * w - 1) / (4 * w));
     });
     if (grid) *grid = p->ctx->wave_grid;
     if (max_pieces_per_wave) *max_pieces_per_wave = most;
-    return count;
+    return xg_plan_kind_launches(p, XG_COPY_WAVE);
 }
 
-// The launches of one run (xg_plan_launches' dispatches counted once each) that go to
-// copy_kernel_s, the shifted piece copy.
-extern "C" int xg_plan_shift_launches(const xg_plan *p)
-{
-    int count = 0;
-    each_launch(p, [&](const CopyLaunch &l) { count += l.shift; });
-    return count;
-}
+extern "C" int xg_plan_shift_launches(const xg_plan *p) { return xg_plan_kind_launches(p, XG_COPY_SHIFT); }
+extern "C" int xg_plan_extent_launches(const xg_plan *p) { return xg_plan_kind_launches(p, XG_COPY_EXTENT); }
 
-// ... those that go to copy_kernel_q, the small-piece copy of large uniform launches (*kib: their
-// piece size, 0 when there is none; may be NULL) ...
+// *kib: the SMALL launches' piece size, 0 when there is none; may be NULL
 extern "C" int xg_plan_small_launches(const xg_plan *p, int *kib)
 {
-    int count = 0, q = 0;
+    if (kib) *kib = 0;
     each_launch(p, [&](const CopyLaunch &l) {
-        count += l.q != 0;
-        if (l.q) q = l.q;
+        if (kib && l.kind == XG_COPY_SMALL) *kib = l.kib;
     });
-    if (kib) *kib = 4 * q;
-    return count;
-}
-
-// ... and those that go to copy_kernel_x, the extent copy of placement plans.
-extern "C" int xg_plan_extent_launches(const xg_plan *p)
-{
-    int count = 0;
-    each_launch(p, [&](const CopyLaunch &l) { count += l.ext; });
-    return count;
+    return xg_plan_kind_launches(p, XG_COPY_SMALL);
 }
 
 static int enqueue_step(xg_plan *p, int s)

@@ -511,100 +511,69 @@ struct TableBuilder {
         return n;
     }
 
-    // Open launch `l` over the copies of `ranges`: its first piece, bytes, kernel form and the
-    // size its pieces are cut to.
-    // One piece per workgroup.  Bytes per piece: c->chunk (32 KiB: profiles/r01_copy_ab.txt) or
-    // c->chunk / 2, / 4, / 8 (>= 4 KiB; a halving keeps dividing the power-of-two segment sizes:
-    // no ragged tail piece per segment, profiles/r01_min_pieces_ab.txt), whichever gives the least
-    // work to the busiest CU: a launch of w pieces of c bytes puts ceil(w / CUs) pieces on some
-    // CU, each costing c bytes plus a fixed per-workgroup start (kWgCost = 2 KiB
-    // bytes-equivalent); ties keep the larger piece.  A 28 MiB pack of 256 KiB segments: 896
+    // Open launch `l` over the copies of `ranges`: its first piece, its bytes, its kernel kind and
+    // the size its pieces are cut to.  Three steps: the facts of the launch, gathered in one pass
+    // over its copies; the choice, by xg_copy_launch_choose (libxghost, pieces.c -- the precedence
+    // of the five kinds is written there, in xg_sched.h, and nowhere else); the choice recorded.
+    // One piece per workgroup.  Bytes per piece (xg_piece_size): rules.chunk (32 KiB:
+    // profiles/r01_copy_ab.txt) or chunk / 2, / 4, / 8 (>= 4 KiB; a halving keeps dividing the
+    // power-of-two segment sizes: no ragged tail piece per segment, profiles/r01_min_pieces_ab.txt),
+    // whichever gives the least work to the busiest CU: a launch of w pieces of c bytes puts
+    // ceil(w / CUs) pieces on some CU, each costing c bytes plus a fixed per-workgroup start (kWgCost
+    // = 2 KiB bytes-equivalent); ties keep the larger piece.  A 28 MiB pack of 256 KiB segments: 896
     // pieces of 32 KiB = 3.5 per CU (the busiest 4 x 32 KiB) -> 1792 of 16 KiB = exactly 7
     // (7 x 16 KiB).  The bench's 448 MiB launches stay 32 KiB (56 per CU).  (A rule forcing
     // >= 2 x CUs pieces on small launches was measured 3-7 % slower and dropped:
     // profiles/r03/min_wg/summary.txt.)
     // `cross`: a launch of a cross-GPU step (packs, unpacks, its local part), or of a GPU-local
-    // step too large for the step engine.  One that copies with plain loads and stores, every
-    // transfer 16-B aligned, of wave_min .. kWaveMax bytes, is cut into pieces of 8 / 4 / 2 KiB
-    // (wave_kib_for; profiles/r03/wave_copy/) and runs copy_kernel_w.
+    // step too large for the step engine: a WAVE launch when plain, aligned and of wave_min ..
+    // kWaveMax bytes (profiles/r03/wave_copy/).
     // `reread` (copy_variant) comes twice: for the cut of the pieces and for the kernel.  They
     // differ in one launch only (step(), the local + pack launch); where the cut says plain and
     // the kernel non-temporal, the wave-sized pieces run copy_kernel_g<4, true>.
-    // `may_small`: a step's own local (+ pack) launch.  When it is UNIFORM -- every positive copy the
-    // same length --, 16-B aligned, holds no pack (a pack's staging side is patched per piece by the
-    // device scan), would run copy_kernel_g<4> and moves >= small_piece_min bytes, it runs
-    // copy_kernel_q instead: pieces of small_kib KiB found by index arithmetic, its copies listed as
-    // rows (add), no piece cut at all.  The bench's 448 MiB launches: 114,688 / 57,344 workgroups
-    // from 448 rows.  XG_SMALL_PIECES=0: never.
+    // `may_small`: a step's own local (+ pack) launch, SMALL when it is uniform, aligned, holds no
+    // pack and moves >= small_piece_min bytes: its copies are listed as rows (add), no piece is cut
+    // at all.  The bench's 448 MiB launches: 114,688 / 57,344 workgroups from 448 rows.
     void open(CopyLaunch &l, std::initializer_list<Range> ranges, bool cross, bool reread_cut, bool reread_run,
               bool may_small = false)
     {
-        const xg_ctx *c = p->ctx;
+        const xg_copy_rules &r = p->ctx->rules;
         cur = &l;
         l.b = (int)pieces.size();
-        chunk = c->chunk;
-        uint64_t bits = 0;
+        chunk = r.chunk;
+        xg_launch_facts f{};
         std::vector<int64_t> lens;
         for (const Range &rg : ranges)
             for (int i = 0; i < rg.second; ++i) {
-                const xg_copy &cp = dp->copies[rg.first + i];
-                lens.push_back(cp.len);
-                if (cp.len <= 0) continue;
-                l.bytes += cp.len;
-                bits |= (uint64_t)cp.src_off | (uint64_t)cp.dst_off | (uint64_t)cp.len;
+                lens.push_back(dp->copies[rg.first + i].len);
+                xg_launch_facts_add(&f, &dp->copies[rg.first + i]);
             }
+        l.bytes = f.bytes;
         if (l.bytes <= 0) return;
-        const int v = copy_variant(p, l.bytes, reread_run);
-        l.nt = v == 6;
-        l.stamps = v == 1 || v == 6;
-        // A ragged plan's launch with a piece off the 16-B grid: copy_kernel_s for all its pieces
-        // (region bases are 16-B aligned, xg_regions_adopt insists; every cut below is a multiple
-        // of 16, so a copy's pieces keep its phases).  The cut, the
-        // stream and the stamps stay as they are; a wave launch is aligned and never gets here.
-        l.shift = (dp->flags & XG_DP_RAGGED) && c->ragged_copy && (bits & 15) != 0;
-        // A placement plan's launch of short copies (mean positive length <= extent_mean_max):
-        // copy_kernel_x, one workgroup per TILE of pieces (tile_launches, after the pieces are
-        // ordered and the dispatches cut).  The cut, the ordering, the stream and the stamps stay.
-        int64_t npos = 0;
-        for (int64_t n : lens) npos += n > 0;
-        l.ext = (dp->flags & XG_DP_EXTENTS) && c->extent_copy && l.stamps && c->chunk <= (1 << 24) &&
-                l.bytes <= npos * c->extent_mean_max;
-        if (l.ext) l.shift = false;
-        if (!l.ext && cross && l.bytes >= c->wave_min && l.bytes <= kWaveMax && (bits & 15) == 0 &&
-            copy_variant(p, l.bytes, reread_cut) == 1) {
-            const int kib = c->wave_kib ? c->wave_kib : wave_kib_for(l.bytes, c->cus);
-            chunk = (int64_t)kib << 10;
-            if (v == 1) l.kib = kib;
-        } else {
-            chunk = xg_piece_size(lens.data(), (int)lens.size(), c->chunk, c->cus, kWgCost);
+        f.lens = lens.data();
+        f.nlens = (int)lens.size();
+        f.dp_flags = dp->flags;
+        f.cross = cross;
+        f.may_small = may_small;
+        f.nt_cut = copy_variant(p, l.bytes, reread_cut) == 6;
+        f.nt_run = copy_variant(p, l.bytes, reread_run) == 6;
+        xg_copy_choice ch;
+        xg_copy_launch_choose(&f, &r, &ch);         // bytes > 0: it cannot refuse
+        l.kind = ch.kind;
+        l.nt = ch.nt;
+        l.kib = ch.kib;
+        chunk = ch.piece;
+        if (l.kind == XG_COPY_SMALL) {
+            l.q_len = f.uniform_len;
+            l.q_k = ch.order;
+            l.q_row = (int)p->rows.size();
         }
-        if (!may_small || !c->small_pieces || l.ext || l.shift || l.kib || !l.stamps || (bits & 15) != 0 ||
-            l.bytes < c->small_piece_min)
-            return;
-        int64_t len = 0;
-        bool uniform = true;
-        for (const Range &rg : ranges)
-            for (int i = 0; i < rg.second; ++i) {
-                const xg_copy &cp = dp->copies[rg.first + i];
-                if (cp.len <= 0) continue;
-                uniform = uniform && (len == 0 || cp.len == len) && cp.dst_buf != XG_BUF_STAGE_SEND &&
-                          cp.src_buf != XG_BUF_STAGE_RECV;
-                len = cp.len;
-            }
-        const int64_t piece = (int64_t)c->small_kib << 10;
-        const int64_t ppc = (len + piece - 1) / piece;
-        // xg_small_index works in 32 bits: the launch's workgroups and a group's
-        if (!uniform || npos * ppc > INT32_MAX || c->small_order * ppc > INT32_MAX) return;
-        l.q = c->small_kib / 4;
-        l.q_len = len;
-        l.q_k = c->small_order;
-        l.q_row = (int)p->rows.size();
     }
     // a copy_kernel_q launch: its rows in destination order (order_pieces, for a launch without pieces)
     void close()
     {
         cur->n = (int)pieces.size() - cur->b;
-        if (!cur->q) return;
+        if (cur->kind != XG_COPY_SMALL) return;
         cur->q_copies = (int)p->rows.size() - cur->q_row;
         std::stable_sort(p->rows.begin() + cur->q_row, p->rows.end(),
                          [](const xgk::DCopy &x, const xgk::DCopy &y) { return x.dst < y.dst; });
@@ -620,7 +589,7 @@ struct TableBuilder {
         if (cp.src_off < 0 || cp.dst_off < 0 || cp.src_off + cp.len > r->bytes[cp.src_buf] ||
             cp.dst_off + cp.len > r->bytes[cp.dst_buf])
             return false;
-        if (cur->q) {        // one row per copy; the kernel cuts it (open() let no pack or unpack in)
+        if (cur->kind == XG_COPY_SMALL) {        // one row per copy; the kernel cuts it (open() let no pack or unpack in)
             p->rows.push_back({r->ptr[cp.src_buf] + cp.src_off, r->ptr[cp.dst_buf] + cp.dst_off, cp.len});
             return side < 0;
         }
@@ -719,7 +688,7 @@ struct TableBuilder {
         if (!add_range(r_local, -1)) return false;
         st.local_n = (int)pieces.size() - st.local_b;
         st.local_bytes = span(st.local_b);
-        if (local.q) {       // rows, not pieces
+        if (local.kind == XG_COPY_SMALL) {       // rows, not pieces
             st.small = true;
             st.local_bytes = local.bytes;
         }
@@ -748,7 +717,7 @@ struct TableBuilder {
         // of sharing HBM with the packs (XG_SPLIT_AFTER_PACK=0: both at once, as in round 2)
         std::vector<CopyLaunch> &tab = p->launches;
         auto push = [&](const CopyLaunch &l) {
-            if (l.n > 0 || l.q) tab.push_back(l);
+            if (l.n > 0 || l.kind == XG_COPY_SMALL) tab.push_back(l);
         };
         const bool pack_first = st.fused || c->split_after_pack;
         st.l_b = (int)tab.size();
@@ -808,7 +777,7 @@ static void order_pieces(const xg_plan *p, std::vector<xgk::DCopy> &pieces, Disp
 // bytes of each dispatch (kernel-timing sessions) are summed here once, through the index function.
 static void cut_small(xg_plan *p, CopyLaunch &l)
 {
-    const int64_t cap = p->ctx->launch_max, piece = (int64_t)l.q * xgk::kTile;
+    const int64_t cap = p->ctx->launch_max, piece = (int64_t)l.kib << 10;
     const int64_t W = (int64_t)l.q_copies * xg_small_ppc(l.q_len, piece);
     l.cut = (int)p->cuts.size();
     p->cuts.push_back(0);
@@ -838,7 +807,7 @@ static void cut_launches(xg_plan *p)
     const int64_t cap = p->ctx->launch_max;
     const int64_t *pre = p->plen.data();        // prefix sums of the piece lengths
     for (CopyLaunch &l : p->launches) {
-        if (l.q) {
+        if (l.kind == XG_COPY_SMALL) {
             cut_small(p, l);
             continue;
         }
@@ -867,7 +836,7 @@ static bool tile_launches(xg_plan *p)
     std::vector<int64_t> lens;
     std::vector<int32_t> begin;
     for (CopyLaunch &l : p->launches) {
-        if (!l.ext) continue;
+        if (l.kind != XG_COPY_EXTENT) continue;
         l.xt = (int)p->xt_off.size();
         for (int k = 0; k < l.ndisp; ++k) {
             const int b = p->cuts[l.cut + k], n = p->cuts[l.cut + k + 1] - b;
@@ -885,7 +854,7 @@ static bool tile_launches(xg_plan *p)
 }
 
 // Chains (xg_plan::chain_end).  A chain step: no engine segment's, no RCCL, no unpack, no
-// barrier, and every launch of it on the main stream with a kernel that can stamp its start.
+// barrier, and every launch of it on the main stream (every copy kernel can stamp its start).
 static bool find_chains(xg_plan *p)
 {
     auto chain_step = [&](int s) {
@@ -895,7 +864,7 @@ static bool find_chains(xg_plan *p)
             return false;
         for (int i = st.l_b; i < st.l_e; ++i) {
             const CopyLaunch &l = p->launches[i];
-            if (l.side || l.mark_prev || !l.stamps) return false;
+            if (l.side || l.mark_prev) return false;
         }
         return true;
     };

@@ -119,7 +119,8 @@ struct xg_ctx {
     hipStream_t side;       // local gather/scatter of a step that also talks to other GPUs (overlaps RCCL)
     ncclComm_t comm;
     double *d_red;          // device scratch for barrier / MAX reductions
-    int64_t chunk;          // bytes per copy workgroup
+    xg_copy_rules rules;    // what decides each copy launch's kernel and piece size (xg_copy_launch_choose,
+                            // xg_sched.h): chunk, cus, the wave / ragged / extent / small-piece knobs
     int64_t engine_max_step;   // GPU-local plans whose largest step moves <= this many bytes use the step engine
     int engine_wmax;           // at most this many (co-resident) engine workgroups
     int engine_drain;          // 1: always drain before each barrier arrival (XG_ENGINE_DRAIN=1)
@@ -128,11 +129,7 @@ struct xg_ctx {
     int solo_rails;            // solo segments deal their pieces over up to this many rails
     int solo_waves;            // waves per rail: 16 (a workgroup) or 1
     int64_t launch_max;        // copy launches above this many bytes go as back-to-back launches of ~this size
-    int64_t wave_min;          // cross-GPU steps' plain copy launches of >= this many bytes (and <= kWaveMax)
-                               // run copy_kernel_w (TableBuilder::open)
     int wave_grid;             // copy_kernel_w workgroups resident at once (occupancy x CUs)
-    int wave_kib;              // XG_WAVE_KIB: copy_kernel_w piece KiB forced (2 / 4 / 8), 0 = by launch bytes
-    int cus;                   // compute units
     int step_chain;            // 1: time runs of one-launch local steps by in-kernel stamps (xg_plan_run)
     int engine_arm;            // 1: xg_plan_run arms single-segment plans (doorbell)
     int64_t split_min;         // a cross-GPU step's local gather of >= this many bytes runs on the side stream
@@ -143,15 +140,8 @@ struct xg_ctx {
     int graph;                 // hipGraph replay of multi-launch runs: 1 always, 0 never, -1 latency-bound one-GPU runs
     double wall_hz;            // wall_clock64() rate
     int variant;            // copy kernel variant (copy_variant in plan_load.hip)
-    int ragged_copy;        // 1: a ragged plan's misaligned launches run copy_kernel_s; 0 (XG_RAGGED_COPY=0): copy_kernel_g
-    int extent_copy;        // 1: a placement plan's (XG_DP_EXTENTS) launches of short copies run copy_kernel_x
-    int64_t extent_mean_max;   // ... when the launch's mean positive copy length is <= this (kExtMeanMax)
     int64_t extent_tile;       // bytes per copy_kernel_x tile (kExtTileBytes)
     int engine_occ;            // co-resident step-engine workgroups the device admits (plan load caps W)
-    int small_pieces;          // 1: large uniform launches run copy_kernel_q (XG_SMALL_PIECES; TableBuilder::open)
-    int64_t small_piece_min;   // ... from this many bytes up (kSmallMin; XG_SMALL_PIECE_MIN, a test hook, lowers it)
-    int small_kib;             // their piece size, 4 or 8 KiB (kSmallKiB; XG_SMALL_PIECE_KIB, for the A/B)
-    int small_order;           // copies per group of their piece order (xg_small_index's k; XG_SMALL_PIECE_ORDER, A/B)
     // kernel timing session (xg_ktime_begin/end): 1 = an event pair around every
     // copy launch, 2 = one pair around the whole session on the main stream
     int kt_mode;
@@ -175,22 +165,19 @@ struct xg_regions {
 struct CopyLaunch {
     int b = 0, n = 0;                // pieces [b, b + n) of the plan's piece table
     int64_t bytes = 0;               // bytes they copy (read + written once)
-    int kib = 0;                     // 2 / 4 / 8: copy_kernel_w<kib> over pieces of <= kib KiB; 0: copy_kernel_g<4>
-    bool nt = false;                 // copy_kernel_g<4, true>: non-temporal loads and stores
-    bool shift = false;              // copy_kernel_s<nt> for all its pieces: a launch of a ragged plan
-                                     // (XG_DP_RAGGED) with a piece off the 16-B grid (TableBuilder::open)
-    bool ext = false;                // copy_kernel_x<nt>: a launch of short copies of a placement plan
-                                     // (XG_DP_EXTENTS; TableBuilder::open), one workgroup per TILE of pieces:
-                                     // dispatch k's tiles are xg_plan::xt_begin[xt_off[xt + k] ..], xt_n[xt + k] of them
+    int kind = XG_COPY_PIECE;        // its ONE kernel (xg_copy_launch_choose, xg_sched.h): PIECE copy_kernel_g<4, nt>,
+                                     // WAVE copy_kernel_w<kib>, SHIFT copy_kernel_s<nt>, EXTENT copy_kernel_x<nt>,
+                                     // SMALL copy_kernel_q<kib / 4, nt>; every one can stamp its start (chains)
+    bool nt = false;                 // non-temporal loads and stores (never WAVE)
+    int kib = 0;                     // piece KiB of a WAVE (2 / 4 / 8) or SMALL (4 / 8) launch, else 0
+    // EXTENT only: one workgroup per TILE of pieces -- dispatch k's tiles are
+    // xg_plan::xt_begin[xt_off[xt + k] ..], xt_n[xt + k] of them (tile_launches)
     int xt = 0;
-    int q = 0;                       // 1 / 2: copy_kernel_q<q, nt> -- a uniform, aligned launch in pieces of q x 4 KiB
-                                     // (TableBuilder::open).  It has NO pieces (n = 0): its copies are rows
-                                     // [q_row, q_row + q_copies) of xg_plan::d_rows, each q_len bytes, taken q_k to
-                                     // a group (xg_small_index); its cuts are workgroup indices from 0, and
-                                     // dispatch k copies xg_plan::qbytes[q_bytes + k] bytes
+    // SMALL only: the launch has NO pieces (n = 0); its copies are rows [q_row, q_row + q_copies) of
+    // xg_plan::d_rows, each q_len bytes, taken q_k to a group (xg_small_index); its cuts are workgroup
+    // indices from 0, and dispatch k copies xg_plan::qbytes[q_bytes + k] bytes
     int q_row = 0, q_copies = 0, q_k = 1, q_bytes = 0;
     int64_t q_len = 0;
-    bool stamps = false;             // its kernel can stamp its start (a chain step's launch must)
     bool side = false;               // runs on the side stream: fork event before it, join event after it
     bool mark_prev = false;          // holds the previous step's unpacks: that step's mark goes right behind it
     int cut = 0, ndisp = 1;          // its dispatches (launches above 1.5 x launch_max go as several):
@@ -261,7 +248,7 @@ struct xg_plan {
     std::vector<int32_t> call_begin;        // nsteps + 1: where each step's calls start
     std::vector<CopyLaunch> launches;       // every step's copy launches (StepR::l_b .. l_e), fixed at load
     std::vector<int> cuts;                  // their dispatches' piece boundaries (CopyLaunch::cut)
-    // copy_kernel_x tile tables, one per dispatch of every `ext` launch (xg_extent_tiles over the
+    // copy_kernel_x tile tables, one per dispatch of every EXTENT launch (xg_extent_tiles over the
     // dispatch's ordered pieces): xt_n[i] tiles, tile t = pieces [xt_begin[xt_off[i] + t], .. + t + 1])
     // of the dispatch (indices relative to its first piece); d_xt: xt_begin on the device
     std::vector<int> xt_begin, xt_off, xt_n;
@@ -384,16 +371,6 @@ constexpr int kSmallKiB = 8;
 constexpr int kSmallOrder = 8;
 constexpr int kSmallDefault = 1;
 constexpr int64_t kWaveMax = 32 << 20;     // copy_kernel_w up to this launch size (profiles/r03/wave_local/)
-// Piece KiB of a copy_kernel_w launch of `bytes`: the largest of 8 / 4 / 2 that still gives every
-// CU a 4-wave workgroup (bytes / piece >= 4 x CUs): a 4 MiB launch in 8 KiB pieces is 512 waves =
-// 128 workgroups, half the chip (the local part of a configs[2] step, profiles/r05/share_launches/);
-// in 4 KiB pieces it is 256 workgroups.  Smaller launches take 2 KiB pieces.
-static inline int wave_kib_for(int64_t bytes, int cus)
-{
-    for (int kib = 8; kib > 2; kib /= 2)
-        if (bytes / ((int64_t)kib << 10) >= 4 * (int64_t)cus) return kib;
-    return 2;
-}
 
 // RCCL writes its log -- and, under NCCL_DEBUG=WARN/VERSION, a version banner at
 // communicator creation -- to stdout unless NCCL_DEBUG_FILE says otherwise; stdout

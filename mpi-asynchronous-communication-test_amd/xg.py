@@ -109,6 +109,32 @@ class Ext(C.Structure):
     _fields_ = [("rank", C.c_int32), ("agg", C.c_int32), ("off", C.c_int64), ("len", C.c_int64)]
 
 
+class LaunchFacts(C.Structure):
+    """xg_launch_facts: what one copy launch is"""
+    _fields_ = [("bytes", C.c_int64), ("npos", C.c_int64), ("bits", C.c_uint64), ("uniform_len", C.c_int64),
+                ("lens", C.POINTER(C.c_int64)), ("nlens", C.c_int32), ("dp_flags", C.c_int32), ("cross", C.c_int32),
+                ("may_small", C.c_int32), ("nt_cut", C.c_int32), ("nt_run", C.c_int32)]
+
+
+class CopyRules(C.Structure):
+    """xg_copy_rules: the context's knobs; the defaults are the runtime's on a 256-CU device"""
+    _fields_ = [("chunk", C.c_int64), ("wave_min", C.c_int64), ("wave_max", C.c_int64), ("wg_cost", C.c_int64),
+                ("extent_mean_max", C.c_int64), ("small_piece_min", C.c_int64), ("cus", C.c_int32),
+                ("wave_kib", C.c_int32), ("ragged_copy", C.c_int32), ("extent_copy", C.c_int32),
+                ("small_pieces", C.c_int32), ("small_kib", C.c_int32), ("small_order", C.c_int32)]
+    DEFAULTS = dict(chunk=32768, wave_min=1 << 20, wave_max=32 << 20, wg_cost=2048, extent_mean_max=1024,
+                    small_piece_min=112 << 20, cus=256, wave_kib=0, ragged_copy=1, extent_copy=1, small_pieces=1,
+                    small_kib=8, small_order=8)
+
+
+class CopyChoice(C.Structure):
+    """xg_copy_choice"""
+    _fields_ = [("kind", C.c_int32), ("nt", C.c_int32), ("kib", C.c_int32), ("order", C.c_int32), ("piece", C.c_int64)]
+
+
+COPY_PIECE, COPY_WAVE, COPY_SHIFT, COPY_EXTENT, COPY_SMALL, COPY_NKIND = range(6)   # xg_sched.h XG_COPY_*
+
+
 class RunOpts(C.Structure):
     """xg_run_opts"""
     _fields_ = [("verify", C.c_int), ("fingerprint", C.c_int), ("eager_limit", C.c_int64),
@@ -204,6 +230,9 @@ def host():
         h.xg_piece_size.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_int, C.c_int64]
         h.xg_extent_tiles.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int32)]
         h.xg_small_piece_at.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int] + [C.POINTER(C.c_int64)] * 3
+        h.xg_launch_facts_add.restype = None
+        h.xg_launch_facts_add.argtypes = [C.POINTER(LaunchFacts), C.POINTER(Copy)]
+        h.xg_copy_launch_choose.argtypes = [C.POINTER(LaunchFacts), C.POINTER(CopyRules), C.POINTER(CopyChoice)]
         h.xg_exts_lens.argtypes = [C.POINTER(Ext), C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]
         h.xg_exts_check.argtypes = [C.POINTER(Ext), C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int,
                                     C.c_char_p, C.c_size_t]
@@ -365,6 +394,28 @@ def extent_tiles(lens, tile_bytes=32768, tile_pieces=256):
     begin = (C.c_int32 * (nt + 1))()
     assert host().xg_extent_tiles(arr, n, tile_bytes, tile_pieces, begin) == nt
     return list(begin)
+
+
+def launch_facts(copies, dp_flags=0, cross=False, may_small=False, nt_cut=False, nt_run=False):
+    """xg_launch_facts of one copy launch over copies = [(src_buf, src_off, dst_buf, dst_off, len)],
+    gathered as plan load gathers them (xg_launch_facts_add per copy)"""
+    f = LaunchFacts()
+    f._lens = (C.c_int64 * max(1, len(copies)))(*[c[4] for c in copies])
+    for sb, so, db, do, n in copies:
+        host().xg_launch_facts_add(C.byref(f), C.byref(Copy(so, do, n, sb, db)))
+    f.lens, f.nlens = C.cast(f._lens, C.POINTER(C.c_int64)), len(copies)
+    f.dp_flags, f.cross, f.may_small, f.nt_cut, f.nt_run = dp_flags, cross, may_small, nt_cut, nt_run
+    return f
+
+
+def copy_launch_choose(facts, **rules):
+    """xg_copy_launch_choose: the kernel kind of one copy launch -> (kind, nt, kib, order, piece
+    bytes), or None when it refuses (a launch without bytes); rules: fields of CopyRules over
+    its DEFAULTS"""
+    r, ch = CopyRules(**dict(CopyRules.DEFAULTS, **rules)), CopyChoice()
+    if host().xg_copy_launch_choose(C.byref(facts), C.byref(r), C.byref(ch)) != 0:
+        return None
+    return ch.kind, ch.nt, ch.kib, ch.order, ch.piece
 
 
 def small_piece_at(b, copies, length, piece, k=1):
@@ -744,6 +795,7 @@ def device():
         d.xg_plan_check.argtypes = [vp]
         d.xg_plan_launches.argtypes = [vp]
         d.xg_plan_engine_steps.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
+        d.xg_plan_kind_launches.argtypes = [vp, ip]
         d.xg_plan_wave_launches.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
         d.xg_plan_shift_launches.argtypes = [vp]
         d.xg_plan_extent_launches.argtypes = [vp]
@@ -884,6 +936,18 @@ def plan_wave_launches(plan):
     g, m = C.c_int(), C.c_int()
     n = device().xg_plan_wave_launches(plan, C.byref(g), C.byref(m))
     return n, g.value, m.value
+
+
+def plan_kind_launches(plan):
+    """xg_plan_kind_launches of a loaded plan handle for every kind -> [PIECE, WAVE, SHIFT, EXTENT, SMALL]"""
+    return [device().xg_plan_kind_launches(plan, k) for k in range(COPY_NKIND)]
+
+
+def plan_engine_segments(plan):
+    """the engine segments of a loaded plan handle (xg_plan_engine_steps' *nseg), each one launch"""
+    nseg = C.c_int()
+    device().xg_plan_engine_steps(plan, C.byref(nseg), None)
+    return nseg.value
 
 
 def run_virtual(runs, rccl=False):

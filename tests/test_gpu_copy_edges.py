@@ -29,6 +29,7 @@ def _run_and_compare(xg, cx, steps, send_bytes, recv_bytes, seed, wave=None):
         d = xg.device()
         assert d.xg_plan_engine(sy.p) == 0
         assert d.xg_plan_launches(sy.p) == len(steps)
+        assert sum(xg.plan_kind_launches(sy.p)) == len(steps) - xg.plan_engine_segments(sy.p)
         got_wave = xg.plan_wave_launches(sy.p)
         if wave is None:
             assert got_wave[0] == 0, got_wave

@@ -85,6 +85,8 @@ def _run(xg, cx, steps, send_bytes, recv_bytes, seed, flags, want_counts=None):
         if want_counts is not None:
             for g, w in zip(got_counts, want_counts):
                 assert w is None or g == w, (got_counts, want_counts)
+            if want_counts[0] == len(steps):        # single-dispatch launches: every one has exactly one kind
+                assert sum(xg.plan_kind_launches(sy.p)) == len(steps) - xg.plan_engine_segments(sy.p)
         want = sy.expected()
         got = sy.run()
         _compare(steps, got, want)
@@ -194,6 +196,7 @@ def test_extent_copy_in_a_chain(xg):
         sy = ExtSynth(xg, cx, send_bytes, recv_bytes, steps, seed=43, flags=_flags(xg))
         try:
             assert sy.counts() == (3, 3, 0)
+            assert sum(xg.plan_kind_launches(sy.p)) == len(steps) - xg.plan_engine_segments(sy.p)
             n = len(steps)
             done, post, wall = (C.c_double * n)(), (C.c_double * n)(), C.c_double()
             assert sy.d.xg_plan_run(sy.p, done, post, C.byref(wall)) == 0

@@ -97,6 +97,7 @@ def _run_synth(xg, cx, flags, want_shift, seed):
         d = xg.device()
         assert d.xg_plan_engine(sy.p) == 0
         assert d.xg_plan_launches(sy.p) == len(steps)
+        assert sum(xg.plan_kind_launches(sy.p)) == len(steps) - xg.plan_engine_segments(sy.p)
         assert xg.plan_wave_launches(sy.p)[0] == 0
         assert d.xg_plan_shift_launches(sy.p) == (len(steps) if want_shift else 0)
         want = sy.expected()

@@ -1,5 +1,5 @@
 """GPU: copy_kernel_q, the small-piece copy of large uniform launches (csrc/kernels.h), and its
-routing (TableBuilder::open in csrc/runtime/plan_load.hip).
+routing (xg_copy_launch_choose in csrc/host/pieces.c, called by TableBuilder::open).
 
 The kernel is driven through synthetic one-GPU plans (synth_plan: seeded random SEND, poisoned
 RECV, sources laid out against the destinations' order, a poisoned gap of >= 16 B around every
@@ -53,6 +53,8 @@ def _run(xg, env, steps, send_bytes, recv_bytes, want_small, kib=None, seed=3, l
             assert _small(xg, sy) == (want_small, (kib or 0) if want_small else 0)
             if launches is not None:
                 assert d.xg_plan_launches(sy.p) == launches
+                if launches == len(steps):          # single-dispatch launches: every one has exactly one kind
+                    assert sum(xg.plan_kind_launches(sy.p)) == launches - xg.plan_engine_segments(sy.p)
             want = sy.expected()
             got = sy.run()
             _compare(steps, got, want)                      # RECV over its whole length, gaps still 0xA5

@@ -86,6 +86,31 @@ def test_local_meets_unpacks(xg):
     assert xg.host().xg_step_local_meets_unpacks(C.byref(dp), 0) == -1
 
 
+def test_local_meets_unpacks_at_an_unpack_s_end(xg):
+    """a step without unpacks (none listed, or only empty ones) meets nothing; a local copy that
+    reads or writes the LAST byte an unpack writes meets it, one that starts at the byte after does
+    not -- also when a longer unpack that starts earlier ends there (the running maximum of ends)"""
+    import ctypes as C
+    S, R, SS, SR = xg.BUF_SEND, xg.BUF_RECV, xg.BUF_STAGE_SEND, xg.BUF_STAGE_RECV
+    local = [(S, 0, R, 1000, 100), (R, 5000, S, 200, 50)]
+    for unp in ([], [(SR, 0, R, 1000, 0), (SR, 0, R, 5000, 0)]):
+        dp = _plan(xg, [([], [], [(S, 0, SS, 0, 8)], unp), ([], local, [(S, 0, SS, 0, 8)], [])])
+        assert xg.host().xg_step_local_meets_unpacks(C.byref(dp), 1) == 0, unp
+    unp = [(SR, 0, R, 1000, 100), (SR, 100, R, 1010, 20), (SR, 200, R, 5000, 50)]   # RECV [1000,1100) over [1010,1030)
+    cases = [
+        ([(S, 0, R, 1099, 1)], 1),               # writes an unpack's last byte
+        ([(S, 0, R, 1099, 64)], 1),              # starts on it
+        ([(R, 1099, S, 0, 1)], 1),               # reads it
+        ([(S, 0, R, 1100, 1)], 0),               # the byte after the last
+        ([(S, 0, R, 1100, 64)], 0),
+        ([(R, 1100, S, 0, 8)], 0),               # reads from the byte after
+        ([(R, 5050, S, 0, 8), (S, 0, R, 5049, 1)], 1),
+    ]
+    for local, want in cases:
+        dp = _plan(xg, [([], [], [(S, 0, SS, 0, 150)], unp), ([], local, [(S, 0, SS, 0, 8)], [])])
+        assert xg.host().xg_step_local_meets_unpacks(C.byref(dp), 1) == want, (local, want)
+
+
 def test_real_plans_never_meet_their_unpacks(xg):
     """every golden-shape plan on 2 and 8 GPUs, packed: no local copy touches the previous
     step's unpacked bytes (so the fused launch may take a small local part)"""
