@@ -167,6 +167,14 @@ int xg_plan_engine_rails(const xg_plan *p);
 int xg_plan_engine_steps(const xg_plan *p, int *nseg, int *nhaz);
 /* Kernel launches of one run (copy + engine launches; RCCL's own kernels aside). */
 int xg_plan_launches(const xg_plan *p);
+/* Read-only: the form xg_plan_load gave step s, as bits -- SPLIT: its local copies on the side
+ * stream; FUSED: its packs share a launch with step s-1's unpacks (that step is DEFERRED);
+ * FUSED_LOCAL: its local copies joined that launch; STAGE_FUSED: its stage copies share the local
+ * (+ pack) launch; SELF_LOCAL: its local copies travel in its RCCL group; ENGINE: it runs inside
+ * an engine segment.  -1 for a bad step. */
+enum { XG_FORM_SPLIT = 1, XG_FORM_FUSED = 2, XG_FORM_FUSED_LOCAL = 4, XG_FORM_STAGE_FUSED = 8, XG_FORM_DEFERRED = 16,
+       XG_FORM_SELF_LOCAL = 32, XG_FORM_ENGINE = 64 };
+int xg_plan_step_form(const xg_plan *p, int s);
 /* The copy launches of one run -- entries of the launch table: one of several dispatches counts
  * once -- whose kernel is of `kind` (XG_COPY_PIECE .. XG_COPY_SMALL, xg_sched.h: every launch has
  * exactly one, chosen at load by xg_copy_launch_choose).  The four counters below are this one for

@@ -192,6 +192,17 @@ typedef struct {
                                          launch time out in proportion (xg_plan_run)  */
 } xg_stepplan;
 
+/* What a valid xg_devplan means, whoever built it (xg_plan_load takes any).  Steps run in order.
+ * Inside a step four phases run in order: the stage copies; the other pre copies (local copies,
+ * then packs); the p2p groups (group 0, then group 1); the post copies (unpacks).  The copies of
+ * one phase, and the calls of one p2p group, are simultaneous: none writes bytes another of the
+ * same phase reads or writes.  Phases and steps may depend on each other in any way -- read
+ * after write, write after write with other bytes, write after read -- and the runtime, which
+ * merges and overlaps phases where a host predicate (xg_engine_hazards, xg_engine_rail_safe,
+ * xg_step_*_meet*) finds them independent, must leave every region as that order leaves it.
+ * One limit: a step's LOCAL copies may run beside its own p2p groups and unpacks (on the side
+ * stream, or inside the RCCL group), so they touch no byte those write and write none those read.
+ * tests/dep_plan.py executes exactly these semantics on numpy regions. */
 #define XG_DP_RAGGED 1               /* xg_devplan.flags bit 0: built from a ragged schedule */
 #define XG_DP_EXTENTS 2              /* bit 1: a placement plan (xg_place_plan_build): launches of many
                                         short copies, which the runtime may run on copy_kernel_x */
@@ -381,6 +392,10 @@ int64_t xg_piece_size(const int64_t *lens, int n, int64_t chunk, int cus, int64_
  * reads or writes bytes that step s-1's unpacks write -- then the two may not share one copy
  * launch; 0 if they may; -1 for a bad step (pieces.c). */
 int xg_step_local_meets_unpacks(const xg_devplan *dp, int s);
+/* The same for step s's packs: 1 if one reads bytes that step s-1's unpacks write (it forwards
+ * received bytes: a pack's source may lie in any region) or writes such bytes; 0 if packs and
+ * unpacks may share one copy launch; -1 for a bad step (pieces.c). */
+int xg_step_packs_meet_unpacks(const xg_devplan *dp, int s);
 /* 1 if a pre copy of step s after its stage copies (local gather/scatter, packs) reads or writes
  * bytes a stage copy writes, or writes bytes one reads -- then the stage copies keep a launch of
  * their own; 0 if all may share one launch; -1 for a bad step (pieces.c). */

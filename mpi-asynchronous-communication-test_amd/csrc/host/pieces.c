@@ -234,6 +234,29 @@ int xg_step_local_meets_unpacks(const xg_devplan *dp, int s)
     return hit;
 }
 
+/* Step s's packs against the bytes step s-1's unpacks write: 1 if a pack reads such a byte (a
+ * forward out of RECV or SCRATCH: a pack's source may lie in any region) or writes one (an
+ * unpack into STAGE_SEND; no schedule has one, any xg_devplan may) -- then the packs cannot
+ * share a launch with those unpacks either.  Returns -1 for a bad step. */
+int xg_step_packs_meet_unpacks(const xg_devplan *dp, int s)
+{
+    const xg_stepplan *pv, *sp;
+    ivset w = {{0}, {0}, {0}};
+    int i, hit;
+    if (!dp || s < 1 || s >= dp->nsteps) return -1;
+    pv = &dp->steps[s - 1];
+    sp = &dp->steps[s];
+    hit = ivset_build(&w, dp->copies + pv->post_begin, pv->post_count, 1) != 0;   /* refuse the fusion when in doubt */
+    for (i = sp->stage_count; i < sp->pre_count && !hit; ++i) {
+        const xg_copy *c = &dp->copies[sp->pre_begin + i];
+        if (c->dst_buf != XG_BUF_STAGE_SEND || c->len <= 0) continue;   /* a local copy, or empty */
+        hit = ivset_meets(&w, c->src_buf, c->src_off, c->src_off + c->len) ||
+              ivset_meets(&w, c->dst_buf, c->dst_off, c->dst_off + c->len);
+    }
+    ivset_free(&w);
+    return hit;
+}
+
 /* Step s's stage copies (TAM rank-local memcpy's through SCRATCH) against its other pre copies
  * (local gather/scatter, packs): 1 if one of those reads or writes a byte a stage copy writes,
  * or writes a byte a stage copy reads -- then the stage copies need a launch of their own ahead

@@ -441,11 +441,15 @@ static bool step_forms(xg_plan *p, const xg_devplan *dp)
         // a cross-GPU step's local part runs on the side stream beside the packs and the RCCL
         // group (split) when it is large enough to pay for the fork / join; a smaller one joins
         // the step's first launch -- the fused one too, if it touches none of the bytes the
-        // previous step's unpacks write (then the step is ONE copy launch + its RCCL group)
+        // previous step's unpacks write (then the step is ONE copy launch + its RCCL group).
+        // The fused launch itself holds step s-1's unpacks and this step's packs, its workgroups
+        // in any order: never when a pack reads (forwards) bytes those unpacks write, whatever
+        // becomes of the local part.  A split local part forks behind that launch.
         st.split = st.p2p_n > 0 && nloc > 0 && b_loc >= c->split_min;
         const bool prev_ok = s > 0 && npack > 0 && sp.stage_count == 0 &&
                              !p->steps[s - 1].sync_after && dp->steps[s - 1].post_count > 0;
-        st.fused = prev_ok && (st.split || nloc == 0 || !xg_step_local_meets_unpacks(dp, s));
+        st.fused = prev_ok && xg_step_packs_meet_unpacks(dp, s) == 0 &&
+                   (st.split || nloc == 0 || !xg_step_local_meets_unpacks(dp, s));
         st.fused_local = st.fused && !st.split && nloc > 0;
         // TAM: a step's stage copies share the local (+ pack) launch when none of those meets
         // their bytes -- README m15 / m16 step 3: 6 -> 5 launches per run
@@ -1003,6 +1007,15 @@ extern "C" int xg_plan_engine_rails(const xg_plan *p)
     return 0;
 }
 extern "C" int xg_plan_launches(const xg_plan *p) { return p->nlaunch; }
+
+extern "C" int xg_plan_step_form(const xg_plan *p, int s)
+{
+    if (!p || s < 0 || s >= p->nsteps) return -1;
+    const StepR &st = p->steps[s];
+    return (st.split ? XG_FORM_SPLIT : 0) | (st.fused ? XG_FORM_FUSED : 0) | (st.fused_local ? XG_FORM_FUSED_LOCAL : 0) |
+           (st.stage_fused ? XG_FORM_STAGE_FUSED : 0) | (st.deferred ? XG_FORM_DEFERRED : 0) |
+           (st.self_local ? XG_FORM_SELF_LOCAL : 0) | (p->seg_of[s] >= 0 ? XG_FORM_ENGINE : 0);
+}
 
 extern "C" int xg_plan_engine_steps(const xg_plan *p, int *nseg, int *nhaz)
 {

@@ -193,6 +193,7 @@ struct StepR {
     //   fused: this step's packs go in ONE launch with the previous step's unpacks
     //   (deferred there); a pack only fills staging and delivers nothing, so every
     //   message of this step is still delivered after every one of the previous step.
+    //   Never when a pack reads bytes those unpacks write (xg_step_packs_meet_unpacks).
     // call_b / call_n: the step's RCCL calls in the plan's call list (xg_devplan_step_calls);
     // p2p_n of them are send/recv (one group), sync_after: the last is the in-loop barrier
     int stage_b = 0, stage_n = 0, local_b = 0, local_n = 0, pack_b = 0, pack_n = 0, post_b = 0, post_n = 0;

@@ -225,6 +225,7 @@ def host():
         h.xg_devplans_match.argtypes = [C.POINTER(C.POINTER(DevPlan)), C.c_int, C.c_int64, C.POINTER(CallPair),
                                         C.c_int64, C.c_char_p, C.c_size_t]
         h.xg_step_local_meets_unpacks.argtypes = [C.POINTER(DevPlan), C.c_int]
+        h.xg_step_packs_meet_unpacks.argtypes = [C.POINTER(DevPlan), C.c_int]
         h.xg_step_stage_meets_rest.argtypes = [C.POINTER(DevPlan), C.c_int]
         h.xg_piece_size.restype = C.c_int64
         h.xg_piece_size.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_int, C.c_int64]
@@ -683,6 +684,10 @@ class DevicePlanView:
         """xg_step_local_meets_unpacks: may step's local copies share a launch with step-1's unpacks?"""
         return host().xg_step_local_meets_unpacks(self._p, step)
 
+    def packs_meet_unpacks(self, step):
+        """xg_step_packs_meet_unpacks: does a pack of step forward bytes step-1's unpacks write?"""
+        return host().xg_step_packs_meet_unpacks(self._p, step)
+
     def stage_meets_rest(self, step):
         """xg_step_stage_meets_rest: must step's stage copies keep a launch of their own?"""
         return host().xg_step_stage_meets_rest(self._p, step)
@@ -794,6 +799,7 @@ def device():
         d.xg_plan_engine_rails.argtypes = [vp]
         d.xg_plan_check.argtypes = [vp]
         d.xg_plan_launches.argtypes = [vp]
+        d.xg_plan_step_form.argtypes = [vp, ip]
         d.xg_plan_engine_steps.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
         d.xg_plan_kind_launches.argtypes = [vp, ip]
         d.xg_plan_wave_launches.argtypes = [vp, C.POINTER(ip), C.POINTER(ip)]
@@ -941,6 +947,15 @@ def plan_wave_launches(plan):
 def plan_kind_launches(plan):
     """xg_plan_kind_launches of a loaded plan handle for every kind -> [PIECE, WAVE, SHIFT, EXTENT, SMALL]"""
     return [device().xg_plan_kind_launches(plan, k) for k in range(COPY_NKIND)]
+
+
+FORM_SPLIT, FORM_FUSED, FORM_FUSED_LOCAL, FORM_STAGE_FUSED, FORM_DEFERRED, FORM_SELF_LOCAL, FORM_ENGINE = (
+    1, 2, 4, 8, 16, 32, 64)            # xg.h XG_FORM_*
+
+
+def plan_step_form(plan, step):
+    """xg_plan_step_form of a loaded plan handle: the XG_FORM_* bits of step `step`"""
+    return device().xg_plan_step_form(plan, step)
 
 
 def plan_engine_segments(plan):

@@ -31,6 +31,19 @@ def test_device_library_exports_xg_h(xg):
     assert not missing, missing
 
 
+def test_step_form_accessor_and_pack_predicate_are_declared_and_bound(xg):
+    """xg_plan_step_form (xg.h, with its XG_FORM_* bits) and xg_step_packs_meet_unpacks (xg_sched.h)
+    are part of the ABI, and xg.py's constants are the header's"""
+    assert "xg_plan_step_form" in declared("xg.h") and "xg_step_packs_meet_unpacks" in declared("xg_sched.h")
+    src = open(os.path.join(REPO, "include", "xg.h")).read()
+    bits = dict((k, int(v)) for k, v in re.findall(r"\bXG_FORM_([A-Z_]+) = (\d+)", src))
+    assert bits == {"SPLIT": xg.FORM_SPLIT, "FUSED": xg.FORM_FUSED, "FUSED_LOCAL": xg.FORM_FUSED_LOCAL,
+                    "STAGE_FUSED": xg.FORM_STAGE_FUSED, "DEFERRED": xg.FORM_DEFERRED,
+                    "SELF_LOCAL": xg.FORM_SELF_LOCAL, "ENGINE": xg.FORM_ENGINE}, bits
+    assert sorted(bits.values()) == [1, 2, 4, 8, 16, 32, 64]
+    assert xg.device().xg_plan_step_form.argtypes is not None and xg.host().xg_step_packs_meet_unpacks.argtypes is not None
+
+
 def test_product_does_not_reference_oracle():
     """The product path never imports/links the checker."""
     for root, _dirs, files in os.walk(PKG):
