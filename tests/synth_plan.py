@@ -73,10 +73,12 @@ def _assert_gaps(steps, recv_bytes):
     assert all(b[0] - a[1] >= 16 for a, b in zip(iv, iv[1:]))
 
 
-def _compare(steps, got, want):
+def _compare(steps, got, want, base=0):
+    """got and want: RECV[base .. base + len(got))"""
     if (got == want).all():
         return
-    at = int(np.flatnonzero(got != want)[0])
+    first = int(np.flatnonzero(got != want)[0])
+    at = base + first
     best = None
     for s, st in enumerate(steps):
         for (_sb, so, _db, do, n) in st:
@@ -87,7 +89,7 @@ def _compare(steps, got, want):
     where = "byte %d of" % (at - do) if dist == 0 else "in the gap %d B from" % dist
     pytest.fail("%d bytes differ; the first, RECV[%d] = 0x%02x (expected 0x%02x), is %s the copy of %d B, "
                 "source phase %d, destination phase %d, step %d (RECV[%d..%d))"
-                % (int((got != want).sum()), at, got[at], want[at], where, n, so % 16, do % 16, s, do, do + n))
+                % (int((got != want).sum()), at, got[first], want[first], where, n, so % 16, do % 16, s, do, do + n))
 
 
 WAVE_NP = [1, 3, 4, 6, 255, 256, 257, 262, 517]
@@ -322,6 +324,11 @@ class Synth:
         self.recv = np.full(recv_bytes, 0xA5, np.uint8)
         buf = self.send.tobytes()
         assert d.xg_regions_write(self.r, xg.BUF_SEND, 0, buf, len(buf)) == 0
+        self._load(ctx, send_bytes, recv_bytes, steps)
+
+    def _load(self, ctx, send_bytes, recv_bytes, steps):
+        """the steps as an xg_devplan, loaded over self.r"""
+        xg, d = self.xg, self.d
         copies = [c for st in steps for c in st]
         self.copies = (xg.Copy * max(1, len(copies)))(
             *[xg.Copy(so, do, ln, sb, db) for (sb, so, db, do, ln) in copies])

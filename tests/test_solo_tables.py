@@ -7,7 +7,11 @@ closing the rail's previous step and the one closing its own, and that the rails
 balanced.  Random segments and the real G = 1 plans of the README-config chains."""
 import random
 
+import numpy as np
 import pytest
+
+from sparse_synth import FORMS, SparsePlan, bases, split_steps, window_plan
+from synth_plan import DBASE, SBASE, _segment
 
 
 PIECE, K, MAXP = 1024, 8, 4608
@@ -238,3 +242,158 @@ def test_wide_windows_one_wave_rails(xg, seed, G):
     dsts = [x[1] for st in steps for x in st]
     assert max(srcs) - min(srcs) > (1 << 28) or G == 1     # past the packed form's window
     interpret(steps, rng.choice([1, 16, 512]), min(srcs), min(dsts), xg, WAVES=1, G=G)
+
+
+# ------------------------------------------------------------------ descriptors at the ends of their windows
+# (sparse_synth.py; run on the device by test_gpu_solo_windows.py)
+WINDOW_RAILS = {"P": (1, 3, 16), "W1": (1, 7, 512), "W4": (1, 7, 512), "W16": (1, 7, 512)}
+
+
+def _window_tables(xg, form, steps, rails_max):
+    """the tables of the steps' one segment, from bases of its own: (spans, shape, descs, close, rows)"""
+    f = FORMS[form]
+    so, do = bases(steps)
+    sp = [[(SBASE + a, DBASE + b, n) for (_x, a, _y, b, n) in st] for st in steps]
+    rc, shape, descs, close, _cs, rows = xg.solo_tables(sp, rails_max, SBASE + so, DBASE + do, waves=f["waves"],
+                                                        granule=f["G"])
+    return rc, sp, shape, descs, close, rows
+
+
+def _fields(form, descs, close):
+    """(src, dst, len, before) of every real piece"""
+    f = FORMS[form]
+    out = []
+    for r in range(len(descs)):
+        for i, d in enumerate(descs[r]):
+            x = decode(d, f["G"], close[r][i] if f["waves"] == 1 else None)
+            if x[2]:
+                out.append(x)
+    return out
+
+
+@pytest.mark.parametrize("form,rails", [(fm, r) for fm in FORMS for r in WINDOW_RAILS[fm]])
+def test_window_plans_reach_the_top_of_the_fields(xg, form, rails):
+    """the tables of each window plan build, the interpreter accepts them, and the largest source
+    and destination field is the largest the form can hold: 2^24 - 64 packed, 2^32 - 1024 wide at
+    granule 1 (a 1 KiB piece ending at the window), bit 31 at granules 4 and 16"""
+    f = FORMS[form]
+    steps = _segment(window_plan(form, rails)[0])
+    rc, sp, shape, descs, close, _rows = _window_tables(xg, form, steps, rails)
+    assert rc == 0, shape
+    interpret(sp, rails, SBASE + bases(steps)[0], DBASE + bases(steps)[1], xg, WAVES=f["waves"], G=f["G"])
+    fl = _fields(form, descs, close)
+    top = {"P": (1 << 24) - 64, "W1": (1 << 32) - 1024, "W4": 1 << 31, "W16": 1 << 31}[form]
+    assert max(x[0] for x in fl) == top and max(x[1] for x in fl) == top
+    assert min(x[0] for x in fl) == 0 and min(x[1] for x in fl) == 0
+    for side in (0, 1):                 # every bit of the field is set in some piece and clear in another
+        width = 24 if form == "P" else 32
+        assert all(any(x[side] >> b & 1 for x in fl) and any(not x[side] >> b & 1 for x in fl) for b in range(6, width))
+    if form == "P":
+        # the length field's top bit under a destination's top bit, behind barriers: on one rail
+        # the row of the one-piece steps holds >= 8, with more rails every rail still holds some
+        hi = [x for x in fl if x[1] >= 1 << 23 and x[2] == 64]
+        assert max(x[3] for x in hi) >= (8 if rails == 1 else 1), sorted(x[3] for x in hi)
+        assert {x[2] for x in fl} == {64, 1}          # 1024 B, 16 B, and 1040 B as 64 + 1
+    else:
+        assert {x[2] * f["G"] for x in fl} >= {n for n in f["lens"] if n <= PIECE}
+
+
+@pytest.mark.parametrize("form", ["P", "W1"])
+def test_split_plans_need_bases_per_part(xg, form):
+    """a hull one granule wider than the window: XG_EARG as one table; "steps": rc 0 as the two
+    parts solo_split's greedy cut gives (the part before the cut with one more step does not
+    fit), each from bases of its own; "one_step": step 0 alone is refused, nothing can be cut"""
+    rails = 16 if form == "P" else 512
+    steps, _sb, _rb, cut = split_steps(form, "steps")
+    assert _window_tables(xg, form, steps, rails)[0] == 3
+    assert _window_tables(xg, form, steps[:cut + 1], rails)[0] == 3
+    for part in (steps[:cut], steps[cut:]):
+        rc, sp, _shape, descs, close, _rows = _window_tables(xg, form, part, rails)
+        assert rc == 0
+        interpret(sp, rails, SBASE + bases(part)[0], DBASE + bases(part)[1], xg, WAVES=FORMS[form]["waves"],
+                  G=FORMS[form]["G"])
+        fl = _fields(form, descs, close)
+        assert max(max(x[0] for x in fl), max(x[1] for x in fl)) >= FORMS[form]["window"] // 2    # still high
+    assert bases(steps[:cut]) != bases(steps[cut:])
+    steps, _sb, _rb, _none = split_steps(form, "one_step")
+    assert _window_tables(xg, form, steps, rails)[0] == 3 and _window_tables(xg, form, steps[:1], rails)[0] == 3
+
+
+def _table_stores(form, plan, steps, descs, close, rows, dec=decode, scale=None):
+    """the stores solo_engine_kernel issues for these tables, on the CPU: (RECV offset, bytes) per
+    real piece, the bytes read from the plan's SEND (0 where the plan wrote nothing).  dec: the
+    descriptor decode; scale: granules -> bytes (the kernel's `off << kShift`)."""
+    f = FORMS[form]
+    G, W = f["G"], f["waves"]
+    scale = scale or (lambda off: off * G)
+    so0, do0 = bases(steps)
+
+    def send(at, n):
+        v = np.zeros(n, np.uint8)
+        for lo, src in plan.sources:
+            a, b = max(at, lo), min(at + n, lo + len(src))
+            if a < b:
+                v[a - at:b - at] = src[a - lo:b - lo]
+        return v
+    stores = []
+    for r in range(len(descs)):
+        for row in range(rows[r]):
+            for w in range(W):
+                so, do, ln, _bf = dec(descs[r][row * W + w], G, close[r][row] if W == 1 else None)
+                if ln:
+                    stores.append((do0 + scale(do), send(so0 + scale(so), ln * G)))
+    return stores
+
+
+def _packed(src_mask=0xFFFFFF, dst_shift=24):
+    def dec(d, G=16, row_word=None):
+        _s, _d, ln, bf = decode(d, G, row_word)
+        return d & src_mask, (d >> dst_shift) & 0xFFFFFF, ln, bf
+    return dec
+
+
+def _wide(src_mask=0xFFFFFFFF, dst_shift=32):
+    def dec(d, G, row_word):
+        _s, _d, ln, bf = decode(d, G, row_word)
+        return d & src_mask, (d >> dst_shift) & 0xFFFFFFFF, ln, bf
+    return dec
+
+
+def _shift32(G):
+    k = {16: 4, 4: 2, 1: 0}[G]
+    return lambda off: ((off & 0xFFFFFFFF) << k) & 0xFFFFFFFF       # (uint32_t)off << kShift
+
+
+# (form, decode, granules -> bytes, rejected?)
+MUTANTS = [
+    ("P", _packed(), None, False), ("W1", _wide(), None, False), ("W4", _wide(), None, False),
+    ("W16", _wide(), None, False),
+    ("P", _packed(src_mask=0x7FFFFF), None, True),              # & 0x7FFFFF in place of & 0xFFFFFF
+    ("P", _packed(dst_shift=23), None, True),                   # >> 23 in place of >> 24
+    ("W1", _wide(src_mask=0x7FFFFFFF), None, True),             # the same two in the wide form
+    ("W1", _wide(dst_shift=31), None, True),
+    ("W4", _wide(), _shift32(4), True),                         # a 32-bit (off << kShift)
+    ("W16", _wide(), _shift32(16), True),
+    # 24 bits << 4 and 32 bits << 0 fit 32 bits: (P) and (W1) cannot see that one, (W4) and (W16) exist for it
+    ("P", _packed(), _shift32(16), False), ("W1", _wide(), _shift32(1), False),
+]
+
+
+@pytest.mark.parametrize("form,dec,scale,rejected", MUTANTS,
+                         ids=["%s-%d" % (m[0], i) for i, m in enumerate(MUTANTS)])
+def test_window_plans_reject_a_broken_decode(xg, form, dec, scale, rejected):
+    """the comparison the device runs get (SparsePlan: windows byte for byte, every other span of
+    RECV still poison) over a CPU execution of the tables: the decode as it is passes, a narrowed
+    mask, a shift one short and a 32-bit scaled offset fail, naming a copy"""
+    rails = 3 if form == "P" else 7
+    steps, send_bytes, recv_bytes = window_plan(form, rails)
+    plan = SparsePlan(steps, send_bytes, recv_bytes, seed=4)
+    rc, _sp, _shape, descs, close, rows = _window_tables(xg, form, _segment(steps), rails)
+    assert rc == 0
+    stores = _table_stores(form, plan, _segment(steps), descs, close, rows, dec, scale)
+    if not rejected:
+        plan.judge_stores(stores)
+        return
+    with pytest.raises(pytest.fail.Exception) as e:
+        plan.judge_stores(stores)
+    assert "the copy of" in str(e.value), str(e.value)
