@@ -532,6 +532,112 @@ int64_t xg_domain_bytes(const xg_sched *s, int ngpus, int g, const int64_t *dom_
 xg_devplan *xg_place_plan_build(const xg_sched *s, int ngpus, int g, const xg_ext *exts, int64_t n,
                                 const int64_t *dom_bytes);
 
+/* ---------------------------------------------------------------- strided runs (vecs.c)
+ * The same placement described by STRIDED RUNS, the form a regular file view has (MPI_Type_vector /
+ * MPI_Type_create_subarray: each rank's block of a global array, interleaved row by row with the
+ * other ranks' blocks): a few numbers per (rank, aggregator) pair instead of one xg_ext per row.
+ * Vec v: `count` blocks of `len` bytes of pair (rank, aggregator INDEX agg), block j at byte
+ * off + j * stride of aggregator agg's domain.  The vecs of one pair, in list order, and within a
+ * vec the blocks in order of j, carry consecutive bytes of the pair's segment.  A vec with len == 0
+ * or count == 0 is allowed and ignored (its other fields are not looked at, negative ones aside); a
+ * vec with count == 1 is an xg_ext and its stride is not looked at.  Every rank passes the same list. */
+typedef struct { int32_t rank, agg; int64_t off, len, stride, count; } xg_vec;
+/* The extent list a vec list means -- one xg_ext per block of every positive vec (len > 0 and
+ * count > 0), in order: the DEFINITION of the semantics and the tests' oracle; xg_exchange_w takes its
+ * output.  Nothing else here calls it (it is O(blocks)).  Returns the count
+ * (out may be NULL to query it; at most cap are written), -1 for a negative len, count or (count > 1)
+ * stride, a count that does not fit int64 or an offset past int64. */
+int64_t xg_vecs_expand(const xg_vec *v, int64_t n, xg_ext *out, int64_t cap);
+/* lens[r * cb_nodes + a] += count * len over the positive vecs (= xg_exts_lens of the expansion).
+ * XG_EARG for a positive vec's rank or aggregator out of range, a negative len or count, a product
+ * or a sum past int64. */
+int xg_vecs_lens(const xg_vec *v, int64_t n, int procs, int cb_nodes, int64_t *lens);
+/* Accepts and refuses what xg_exts_check accepts and refuses for the expansion, naming the same kind
+ * of fault in err ("out of range", "negative", "overflow", "past the domain end", "overlap"), without
+ * ever building the expansion: O(n) extra memory, bounds from a vec's last block in O(1).  It also
+ * refuses a negative count, a negative stride (count > 1) and off + (count - 1) * stride + len past
+ * int64.  A gather (scatter == 0) may read a byte twice: any stride >= 0 passes, 0 included.  A
+ * scatter finds every pair of overlapping blocks: inside a vec (stride < len with count > 1), and
+ * between the vecs of one aggregator -- sorted by hull [off, off + (count - 1) * stride + len); a vec
+ * whose hull meets no other is done; a cluster of meeting hulls whose vecs all have count > 1 and one
+ * common stride S is accepted without walking a block when their circular intervals [off mod S,
+ * off mod S + len) are pairwise disjoint on the circle of S (the striped view); any other cluster is
+ * walked block by block in ascending order (a k-way merge through a binary heap, one block per vec in
+ * memory), each block against the one before.  XG_EARG / XG_ENOMEM / XG_OK. */
+int xg_vecs_check(const xg_vec *v, int64_t n, int procs, int cb_nodes, const int64_t *dom_bytes, int scatter,
+                  char *err, size_t errlen);
+/* One table row of a strided placement -- what a copy kernel that derives every block by arithmetic
+ * reads in place of a descriptor per block (only the host half exists: DESIGN.md section 11):
+ * `count` blocks of `len` bytes, block j from src_off + j * src_step of region src_buf to
+ * dst_off + j * dst_step of region dst_buf. */
+typedef struct { int32_t src_buf, dst_buf; int64_t src_off, dst_off, src_step, dst_step, len, count; } xg_vrow;
+/* GPU g's rows: one per positive vec of the aggregators it hosts, in list order (vec_index[k]: row
+ * k's list index; may be NULL), at the offsets xg_place_plan_build gives the expansion's copies --
+ * the dense side advances by len per block from the pair's dense offset plus the bytes of the pair's
+ * earlier vecs, the domain side by stride from xg_domain_offset + off (count == 1: both steps 0).
+ * a2m: the dense side is SEND, the domain RECV; m2a the other way round.  region_bytes (XG_NBUF
+ * entries, may be NULL) as xg_place_plan_build sets them.  Returns the row count (rows may be NULL to
+ * query it), -1 for bad arguments or a list that names a rank or aggregator out of range.  The list
+ * must have passed xg_vecs_check. */
+int64_t xg_vec_rows_build(const xg_sched *s, int ngpus, int g, const xg_vec *v, int64_t n, const int64_t *dom_bytes,
+                          xg_vrow *rows, int64_t *vec_index, int64_t *region_bytes);
+/* Tile arithmetic of a row table, host and device code alike as xg_small_index is (pieces.c holds
+ * the external definitions): how a row's blocks are dealt to workgroups, one TILE of a row each.
+ * Blocks of len <= tile_bytes go
+ * bpt = clamp(tile_bytes / len, 1, tile_pieces) to a tile, lane i of tile t taking block t * bpt + i;
+ * a longer block is cut into ceil(len / tile_bytes) pieces of tile_bytes (the last one shorter), one
+ * piece per tile, lane 0's.  All offsets and products are 64-bit.  xg_vec_row_tiles: a row's tile
+ * count (0 for len <= 0 or count <= 0; INT64_MAX when it does not fit). */
+inline XG_HD int64_t xg_vec_bpt(int64_t len, int64_t tile_bytes, int tile_pieces)
+{
+    const int64_t b = tile_bytes / len;
+    return b < 1 ? 1 : b > tile_pieces ? tile_pieces : b;
+}
+inline XG_HD int64_t xg_vec_row_tiles(int64_t len, int64_t count, int64_t tile_bytes, int tile_pieces)
+{
+    if (len <= 0 || count <= 0 || tile_bytes < 1 || tile_pieces < 1) return 0;
+    if (len <= tile_bytes) {
+        const int64_t bpt = xg_vec_bpt(len, tile_bytes, tile_pieces);
+        return count / bpt + (count % bpt != 0);
+    } else {
+        const int64_t ppb = len / tile_bytes + (len % tile_bytes != 0);
+        return ppb > INT64_MAX / count ? INT64_MAX : ppb * count;
+    }
+}
+/* Piece i (lane i) of tile t of a row: n bytes from src_off to dst_off; n = 0 past the tile's last
+ * piece.  t in [0, xg_vec_row_tiles), i in [0, tile_pieces). */
+typedef struct { int64_t src_off, dst_off, n; } xg_vec_at;
+inline XG_HD xg_vec_at xg_vec_piece_at(int64_t src_off, int64_t dst_off, int64_t src_step, int64_t dst_step,
+                                          int64_t len, int64_t count, int64_t tile_bytes, int tile_pieces, int64_t t,
+                                          int i)
+{
+    xg_vec_at p;
+    p.src_off = p.dst_off = p.n = 0;
+    if (len <= tile_bytes) {
+        const int64_t bpt = xg_vec_bpt(len, tile_bytes, tile_pieces);
+        const int64_t j = t * bpt + i;
+        if (i < bpt && j < count) {
+            p.src_off = src_off + j * src_step;
+            p.dst_off = dst_off + j * dst_step;
+            p.n = len;
+        }
+    } else if (i == 0) {
+        const int64_t ppb = len / tile_bytes + (len % tile_bytes != 0);
+        const int64_t j = t / ppb, o = (t - j * ppb) * tile_bytes;
+        p.src_off = src_off + j * src_step + o;
+        p.dst_off = dst_off + j * dst_step + o;
+        p.n = len - o < tile_bytes ? len - o : tile_bytes;
+    }
+    return p;
+}
+/* xg_vec_piece_at for callers that cannot inline it, range-checked: 0, or -1 when t is no tile of the
+ * row, i no lane of a tile or an argument is out of range (pieces.c). */
+int xg_vec_piece(const xg_vrow *row, int64_t tile_bytes, int tile_pieces, int64_t t, int i, int64_t *src_off,
+                 int64_t *dst_off, int64_t *n);
+/* tile0[k] = the tiles of rows [0, k): n + 1 entries (tile0 may be NULL).  Returns the total, or -1
+ * when it passes INT32_MAX (a launch's workgroups are counted in 32 bits) or an argument is bad. */
+int64_t xg_vec_rows_tiles(const xg_vrow *rows, int64_t n, int64_t tile_bytes, int tile_pieces, int32_t *tile0);
+
 /* fill: `nsegs` consecutive d-byte segments at `off` in the SEND region,
  * segment i = fingerprint(rank, seed0 + i, iter) (prepare_*_data loops). */
 typedef struct { int32_t rank, seed0; int64_t off; int32_t nsegs, pad; } xg_segrun;

@@ -84,6 +84,44 @@ int xg_small_piece_at(int64_t b, int64_t copies, int64_t len, int64_t piece, int
     return 0;
 }
 
+/* ... and of the strided placement's tile arithmetic */
+extern inline int64_t xg_vec_bpt(int64_t len, int64_t tile_bytes, int tile_pieces);
+extern inline int64_t xg_vec_row_tiles(int64_t len, int64_t count, int64_t tile_bytes, int tile_pieces);
+extern inline xg_vec_at xg_vec_piece_at(int64_t src_off, int64_t dst_off, int64_t src_step, int64_t dst_step,
+                                           int64_t len, int64_t count, int64_t tile_bytes, int tile_pieces, int64_t t,
+                                           int i);
+
+/* Lane i of tile t of a row (xg_vec_piece_at, xg_sched.h), range-checked. */
+int xg_vec_piece(const xg_vrow *row, int64_t tile_bytes, int tile_pieces, int64_t t, int i, int64_t *src_off,
+                 int64_t *dst_off, int64_t *n)
+{
+    xg_vec_at p;
+    if (!row || tile_bytes < 1 || tile_pieces < 1 || t < 0 || i < 0 || i >= tile_pieces || row->len <= 0 ||
+        row->count <= 0 || t >= xg_vec_row_tiles(row->len, row->count, tile_bytes, tile_pieces))
+        return -1;
+    p = xg_vec_piece_at(row->src_off, row->dst_off, row->src_step, row->dst_step, row->len, row->count, tile_bytes,
+                        tile_pieces, t, i);
+    if (src_off) *src_off = p.src_off;
+    if (dst_off) *dst_off = p.dst_off;
+    if (n) *n = p.n;
+    return 0;
+}
+
+/* The tile prefix sums of a row table: one workgroup per tile, counted in 32 bits. */
+int64_t xg_vec_rows_tiles(const xg_vrow *rows, int64_t n, int64_t tile_bytes, int tile_pieces, int32_t *tile0)
+{
+    int64_t k, tot = 0;
+    if (n < 0 || (n && !rows) || tile_bytes < 1 || tile_pieces < 1) return -1;
+    for (k = 0; k < n; ++k) {
+        const int64_t t = xg_vec_row_tiles(rows[k].len, rows[k].count, tile_bytes, tile_pieces);
+        if (tile0) tile0[k] = (int32_t)tot;
+        if (t > INT32_MAX - tot) return -1;
+        tot += t;
+    }
+    if (tile0) tile0[n] = (int32_t)tot;
+    return tot;
+}
+
 void xg_launch_facts_add(xg_launch_facts *f, const xg_copy *c)
 {
     if (c->len <= 0) return;

@@ -109,6 +109,25 @@ class Ext(C.Structure):
     _fields_ = [("rank", C.c_int32), ("agg", C.c_int32), ("off", C.c_int64), ("len", C.c_int64)]
 
 
+class Vec(C.Structure):
+    """xg_vec: count blocks of len bytes of pair (rank, aggregator index agg), block j at byte
+    off + j * stride of aggregator agg's domain"""
+    _fields_ = [("rank", C.c_int32), ("agg", C.c_int32), ("off", C.c_int64), ("len", C.c_int64),
+                ("stride", C.c_int64), ("count", C.c_int64)]
+
+
+class VRow(C.Structure):
+    """xg_vrow: one table row of a strided placement -- count blocks of len bytes, block j from
+    src_off + j * src_step of region src_buf to dst_off + j * dst_step of region dst_buf"""
+    _fields_ = [("src_buf", C.c_int32), ("dst_buf", C.c_int32), ("src_off", C.c_int64), ("dst_off", C.c_int64),
+                ("src_step", C.c_int64), ("dst_step", C.c_int64), ("len", C.c_int64), ("count", C.c_int64)]
+
+
+class VecAt(C.Structure):
+    """xg_vec_at"""
+    _fields_ = [("src_off", C.c_int64), ("dst_off", C.c_int64), ("n", C.c_int64)]
+
+
 class LaunchFacts(C.Structure):
     """xg_launch_facts: what one copy launch is"""
     _fields_ = [("bytes", C.c_int64), ("npos", C.c_int64), ("bits", C.c_uint64), ("uniform_len", C.c_int64),
@@ -243,6 +262,19 @@ def host():
         h.xg_domain_bytes.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int64)]
         h.xg_place_plan_build.restype = C.POINTER(DevPlan)
         h.xg_place_plan_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Ext), C.c_int64, C.POINTER(C.c_int64)]
+        h.xg_vecs_expand.argtypes = [C.POINTER(Vec), C.c_int64, C.POINTER(Ext), C.c_int64]
+        h.xg_vecs_expand.restype = C.c_int64
+        h.xg_vecs_lens.argtypes = [C.POINTER(Vec), C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64)]
+        h.xg_vecs_check.argtypes = [C.POINTER(Vec), C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int64), C.c_int,
+                                    C.c_char_p, C.c_size_t]
+        h.xg_vec_rows_build.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Vec), C.c_int64, C.POINTER(C.c_int64),
+                                        C.POINTER(VRow), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        h.xg_vec_rows_build.restype = C.c_int64
+        h.xg_vec_row_tiles.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int]
+        h.xg_vec_row_tiles.restype = C.c_int64
+        h.xg_vec_piece.argtypes = [C.POINTER(VRow), C.c_int64, C.c_int, C.c_int64, C.c_int] + [C.POINTER(C.c_int64)] * 3
+        h.xg_vec_rows_tiles.argtypes = [C.POINTER(VRow), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int32)]
+        h.xg_vec_rows_tiles.restype = C.c_int64
         h.xg_fill_runs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SegRun)]
         h.xg_verify_slots.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Slot)]
         h.xg_deliveries.argtypes = [C.c_void_p, C.c_int, C.POINTER(Delivery)]
@@ -454,6 +486,74 @@ def exts_check(exts, procs, cb_nodes, dom_bytes, scatter=True):
     return rc, err.value.decode()
 
 
+def _vec_array(vecs):
+    """vecs: Vec records or (rank, agg, off, len, stride, count) tuples -> (C array, n)"""
+    v = [e if isinstance(e, Vec) else Vec(*[int(x) for x in e]) for e in vecs]
+    return (Vec * max(1, len(v)))(*v), len(v)
+
+
+def _vrow_array(rows):
+    """rows: VRow records or (src_buf, dst_buf, src_off, dst_off, src_step, dst_step, len, count) tuples"""
+    v = [r if isinstance(r, VRow) else VRow(*[int(x) for x in r]) for r in rows]
+    return (VRow * max(1, len(v)))(*v), len(v)
+
+
+def vecs_expand(vecs):
+    """xg_vecs_expand: the extent list a vec list means, as (rank, agg, off, len) tuples -- one per
+    block of every positive vec, in order (O(blocks): the definition, not a fast path); None when
+    it refuses (a negative len, count or stride, or an offset or count past int64)"""
+    arr, n = _vec_array(vecs)
+    m = host().xg_vecs_expand(arr, n, None, 0)
+    if m < 0:
+        return None
+    out = (Ext * max(1, m))()
+    assert host().xg_vecs_expand(arr, n, out, m) == m
+    return [(e.rank, e.agg, e.off, e.len) for e in out[:m]]
+
+
+def vecs_lens(vecs, procs, cb_nodes):
+    """xg_vecs_lens: the P x A length matrix (row-major) of a vec list; XGError when refused"""
+    arr, n = _vec_array(vecs)
+    out = (C.c_int64 * (procs * cb_nodes))()
+    if host().xg_vecs_lens(arr, n, procs, cb_nodes, out) != 0:
+        raise XGError("xg_vecs_lens: rank or aggregator out of range, negative length or count, or overflow")
+    return list(out)
+
+
+def vecs_check(vecs, procs, cb_nodes, dom_bytes, scatter=True):
+    """xg_vecs_check -> (code, reason): what exts_check says of the expansion, without building it"""
+    arr, n = _vec_array(vecs)
+    dom = (C.c_int64 * max(1, cb_nodes))(*[int(x) for x in dom_bytes])
+    err = C.create_string_buffer(512)
+    rc = host().xg_vecs_check(arr, n, procs, cb_nodes, dom, 1 if scatter else 0, err, 512)
+    return rc, err.value.decode()
+
+
+def vec_row_tiles(length, count, tile_bytes=32768, tile_pieces=256):
+    """xg_vec_row_tiles: the tiles (one workgroup each) of one row of a strided placement"""
+    return host().xg_vec_row_tiles(length, count, tile_bytes, tile_pieces)
+
+
+def vec_piece_at(row, t, i, tile_bytes=32768, tile_pieces=256):
+    """xg_vec_piece: (src_off, dst_off, n) of lane i of tile t of a row (n = 0 past the tile's last
+    piece); None when t is no tile of the row or i no lane"""
+    arr, _n = _vrow_array([row])
+    out = [C.c_int64() for _ in range(3)]
+    if host().xg_vec_piece(arr, tile_bytes, tile_pieces, t, i, *[C.byref(x) for x in out]) != 0:
+        return None
+    return tuple(x.value for x in out)
+
+
+def vec_rows_tiles(rows, tile_bytes=32768, tile_pieces=256):
+    """xg_vec_rows_tiles: the prefix sums of the rows' tile counts (len(rows) + 1 entries); None
+    when the total passes 2^31 - 1"""
+    arr, n = _vrow_array(rows)
+    t0 = (C.c_int32 * (n + 1))()
+    if host().xg_vec_rows_tiles(arr, n, tile_bytes, tile_pieces, t0) < 0:
+        return None
+    return list(t0)
+
+
 def method_label(method):
     lab = host().xg_method_label(method)
     return lab.decode() if lab else None
@@ -594,6 +694,20 @@ class Schedule:
         if not p:
             raise XGError("xg_place_plan_build: out of host memory, or a rank / aggregator out of range")
         return DevicePlanView(self, ngpus, g, 0, plan=p)
+
+    def vec_rows(self, ngpus, g, vecs, dom_bytes):
+        """xg_vec_rows_build: GPU g's rows of this (exchange) schedule for a vec list -> (rows as
+        (src_buf, dst_buf, src_off, dst_off, src_step, dst_step, len, count) tuples, the list index of
+        every row, region_bytes)"""
+        arr, n = _vec_array(vecs)
+        dom = (C.c_int64 * max(1, self.A))(*[int(x) for x in dom_bytes])
+        rb = (C.c_int64 * NBUF)()
+        m = host().xg_vec_rows_build(self._h, ngpus, g, arr, n, dom, None, None, rb)
+        if m < 0:
+            raise XGError("xg_vec_rows_build: out of host memory, or a rank / aggregator out of range")
+        rows, idx = (VRow * max(1, m))(), (C.c_int64 * max(1, m))()
+        assert host().xg_vec_rows_build(self._h, ngpus, g, arr, n, dom, rows, idx, None) == m
+        return ([tuple(getattr(r, f) for f, _t in VRow._fields_) for r in rows[:m]], list(idx)[:m], list(rb))
 
     def domain_offset(self, ngpus, a, dom_bytes):
         """xg_domain_offset: where aggregator index a's domain starts in its GPU's domain buffer"""
