@@ -175,6 +175,8 @@ int xg_plan_launches(const xg_plan *p);
 enum { XG_FORM_SPLIT = 1, XG_FORM_FUSED = 2, XG_FORM_FUSED_LOCAL = 4, XG_FORM_STAGE_FUSED = 8, XG_FORM_DEFERRED = 16,
        XG_FORM_SELF_LOCAL = 32, XG_FORM_ENGINE = 64 };
 int xg_plan_step_form(const xg_plan *p, int s);
+/* The loaded plan's host tables, for xg_plan_tables_dump (xg_sched.h); the plan keeps them. */
+const xg_plan_tables *xg_plan_tables_of(const xg_plan *p);
 /* The copy launches of one run -- entries of the launch table: one of several dispatches counts
  * once -- whose kernel is of `kind` (XG_COPY_PIECE .. XG_COPY_SMALL, xg_sched.h: every launch has
  * exactly one, chosen at load by xg_copy_launch_choose).  The four counters below are this one for

@@ -675,6 +675,61 @@ int xg_summarize_results(int procs, int cb_nodes, int data_size, int comm_size, 
                          int type, const char *filename, const char *prefix,
                          xg_timer timer1, xg_timer max_timer1);
 
+/* ---------------------------------------------------------------- plan tables (plan_tables.cc)
+ * What xg_plan_load makes of a device plan before it touches the device -- the piece, launch,
+ * dispatch-cut, tile and row tables, the displacement fix-ups, the engine segments and the chains --
+ * is host arithmetic over the plan, the knobs below and the regions' bases and sizes.  The runtime
+ * calls the builder inside xg_plan_load; this group lets a test call it with no GPU.
+ * xg_plan_knobs: every context setting the builder reads (the runtime's context holds one, filled
+ * by xg_init from the device and the environment). */
+typedef struct xg_plan_knobs {
+    xg_copy_rules rules;       /* what decides each copy launch's kernel and piece size (xg_copy_launch_choose) */
+    int64_t extent_tile;       /* bytes per copy_kernel_x tile */
+    int64_t engine_max_step;   /* GPU-local steps of <= this many bytes may be engine steps; 0: no step engine */
+    int64_t solo_max;          /* solo segments move <= this many bytes per run */
+    int64_t launch_max;        /* copy launches above 1.5 x this many bytes go as dispatches of ~this size; 0: never */
+    int64_t split_min;         /* a cross-GPU step's local part of >= this many bytes runs on the side stream */
+    int64_t self_max;          /* ... of <= this many bytes goes in the step's RCCL group */
+    int32_t variant;           /* copy kernel variant: 0 by size, 1 plain, 6 non-temporal */
+    int32_t engine_wmax;       /* at most this many (co-resident) grid-engine workgroups */
+    int32_t engine_drain;      /* 1: drain before every barrier arrival */
+    int32_t solo;              /* 0: never the solo engine */
+    int32_t solo_rails;        /* solo segments deal their pieces over up to this many rails */
+    int32_t solo_waves;        /* waves per rail: 16 (a workgroup) or 1 */
+    int32_t wave_grid;         /* copy_kernel_w workgroups resident at once */
+    int32_t step_chain;        /* 1: chains of one-launch local steps */
+    int32_t engine_arm;        /* 1: single-segment plans may be armed */
+    int32_t fuse_stage;        /* 1: stage copies join the step's local launch when hazard-free */
+    int32_t split_after_pack;  /* 1: a split step's local part forks after its pack launch */
+    int32_t rank, nranks;      /* this GPU of how many */
+    int32_t virt;              /* 1: one of nranks GPUs emulated on one device */
+} xg_plan_knobs;
+/* What xg_init sets with an empty environment on a device of `cus` compute units that admits
+ * engine_occ co-resident step-engine workgroups and wave_grid copy_kernel_w workgroups; rank 0 of 1. */
+void xg_plan_knobs_default(xg_plan_knobs *k, int cus, int engine_occ, int wave_grid);
+/* Build the tables of dp for regions of bytes[b] bytes at address base[b].  XG_EARG (with the
+ * runtime's message on stderr) for a descriptor outside its region or a tile table that does not
+ * cover its pieces; *out is then NULL. */
+typedef struct xg_plan_tables xg_plan_tables;
+int xg_plan_tables_build(const xg_devplan *dp, const xg_plan_knobs *k, const uint64_t base[XG_NBUF],
+                         const int64_t bytes[XG_NBUF], xg_plan_tables **out);
+void xg_plan_tables_free(xg_plan_tables *t);
+/* The introspection of a loaded plan (xg.h: xg_plan_nsteps .. xg_plan_engine_steps forward here). */
+int xg_plan_tables_nsteps(const xg_plan_tables *t);
+int xg_plan_tables_launches(const xg_plan_tables *t);
+int xg_plan_tables_step_form(const xg_plan_tables *t, int s);
+int xg_plan_tables_kind_launches(const xg_plan_tables *t, int kind);
+int xg_plan_tables_wave_launches(const xg_plan_tables *t, int *grid, int *max_pieces_per_wave);
+int xg_plan_tables_small_launches(const xg_plan_tables *t, int *kib);
+int xg_plan_tables_shift_launches(const xg_plan_tables *t);
+int xg_plan_tables_extent_launches(const xg_plan_tables *t);
+int xg_plan_tables_engine(const xg_plan_tables *t);
+int xg_plan_tables_engine_rails(const xg_plan_tables *t);
+int xg_plan_tables_engine_steps(const xg_plan_tables *t, int *nseg, int *nhaz);
+/* Every table as text, one record per line in a fixed order, every pointer as region+offset.
+ * Returns the length (without the final NUL); at most cap bytes are written; buf may be NULL. */
+int64_t xg_plan_tables_dump(const xg_plan_tables *t, char *buf, int64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,16 +39,9 @@
 #include <type_traits>
 
 #include "../../include/xg_sched.h"     // xg_small_index: the one host / device function of this file
+#include "dcopy.h"                      // kThreads, DCopy, DFix: shared with the host's table builder
 
 namespace xgk {
-
-constexpr int kThreads = 256;
-
-struct DCopy {          // one workgroup's piece of a transfer (absolute device pointers)
-    const uint8_t *src;
-    uint8_t *dst;
-    int64_t len;
-};
 
 struct DSeg {           // one segment to fingerprint
     int64_t off;
@@ -953,17 +946,7 @@ __global__ __launch_bounds__(WV * 64) void solo_engine_kernel(const unsigned lon
     }
 }
 
-// Piece table fix-up after the scan: piece k of a packed copy c moves
-// [o, o + len) of it; its staging side (dst of a pack, src of an unpack) is
-// staging base + disp[c] + o.
-struct DFix {
-    int piece;          // index into the plan's piece table
-    int copy;           // index into disp[]
-    int64_t off;        // byte offset of the piece inside its copy
-    int side;           // 0: patch dst (pack), 1: patch src (unpack)
-    int pad;
-};
-
+// Piece table fix-up after the scan (DFix, dcopy.h).
 [[maybe_unused]] static __global__ __launch_bounds__(kThreads) void displ_apply_kernel(DCopy *__restrict__ pieces, const DFix *__restrict__ fix,
                                                                int nfix, const int64_t *__restrict__ disp,
                                                                uint8_t *stage_send, uint8_t *stage_recv)

@@ -189,25 +189,32 @@ static int init_ctx(xg_ctx *c, const void *uid)
 {
     warn_folded_knobs();
     const int device = c->device, rank = c->rank, nranks = c->nranks;
-    (void)rank;
-    // c->rules: the knobs of xg_copy_launch_choose (xg_sched.h), from rt.h's constants and the environment
-    c->rules.chunk = 32768; c->variant = 0; c->kt_mode = 0; c->nk = 0; c->kt_bytes = 0;   // profiles/r01_copy_ab.txt
-    c->rules.wg_cost = kWgCost;
-    c->rules.wave_max = kWaveMax;
+    // The plan-table knobs (xg_plan_knobs, the context's base): the device's facts, the defaults
+    // (xg_plan_knobs_default, plan_tables.cc -- each default's measurement is named there), then the
+    // environment.  The engine's grid barrier needs every workgroup resident at once: engine_occ.
+    {
+        int cus = 0, per_cu = 0, w_per_cu = 0;
+        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xgk::step_engine_kernel<16>, xgk::kThreads, 0));
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&w_per_cu, xgk::copy_kernel_w<xgk::kWaveKiB>, xgk::kThreads,
+                                                            0));
+        c->engine_occ = cus * (per_cu < 1 ? 1 : per_cu);
+        xg_plan_knobs_default(c, cus, c->engine_occ, (cus > 0 ? cus : 256) * (w_per_cu < 1 ? 1 : w_per_cu));
+        c->rank = rank; c->nranks = nranks;
+    }
+    c->kt_mode = 0; c->nk = 0; c->kt_bytes = 0;
     const char *env = getenv("XG_COPY_VARIANT");          // 0 by size (default), 1 plain, 6 non-temporal
     if (env && (atoi(env) == 1 || atoi(env) == 6)) c->variant = atoi(env);
     else if (env && atoi(env) != 0) fprintf(stderr, "xg: XG_COPY_VARIANT=%s ignored (0, 1 or 6)\n", env);
     env = getenv("XG_RAGGED_COPY");          // "0": a ragged plan's misaligned launches stay on copy_kernel_g (A/B)
-    c->rules.ragged_copy = !(env && atoi(env) == 0);
+    if (env && atoi(env) == 0) c->rules.ragged_copy = 0;
     // copy_kernel_x for a placement plan's launches of short extents (xg_copy_launch_choose): "0" keeps
     // them on copy_kernel_s.  XG_EXTENT_MEAN_MAX / XG_EXTENT_TILE_KIB: the routing threshold and the
     // tile's byte cap, for the A/B of profiles/extent_copy_ab.py
     env = getenv("XG_EXTENT_COPY");
-    c->rules.extent_copy = env ? atoi(env) != 0 : kExtDefault;
-    c->rules.extent_mean_max = kExtMeanMax;
+    if (env) c->rules.extent_copy = atoi(env) != 0;
     env = getenv("XG_EXTENT_MEAN_MAX");
     if (env && atol(env) > 0) c->rules.extent_mean_max = atol(env);
-    c->extent_tile = kExtTileBytes;
     env = getenv("XG_EXTENT_TILE_KIB");
     if (env && atoi(env) > 0 && atoi(env) <= 1024) c->extent_tile = (int64_t)atoi(env) << 10;
     // copy_kernel_q for large uniform launches (xg_copy_launch_choose): "0" restores copy_kernel_g's
@@ -215,39 +222,19 @@ static int init_ctx(xg_ctx *c, const void *uid)
     // XG_SMALL_PIECE_KIB (4 / 8) and XG_SMALL_PIECE_ORDER (copies per group of the piece order):
     // for the A/B of profiles/small_pieces_ab.sh
     env = getenv("XG_SMALL_PIECES");
-    c->rules.small_pieces = env ? atoi(env) != 0 : kSmallDefault;
-    c->rules.small_piece_min = kSmallMin;
+    if (env) c->rules.small_pieces = atoi(env) != 0;
     env = getenv("XG_SMALL_PIECE_MIN");
     if (env && atoll(env) >= 0) c->rules.small_piece_min = atoll(env);
-    c->rules.small_kib = kSmallKiB;
     env = getenv("XG_SMALL_PIECE_KIB");
     if (env && (atoi(env) == 4 || atoi(env) == 8)) c->rules.small_kib = atoi(env);
-    c->rules.small_order = kSmallOrder;
     env = getenv("XG_SMALL_PIECE_ORDER");
     if (env && atoi(env) >= 1 && atoi(env) <= 1024) c->rules.small_order = atoi(env);
-    c->engine_max_step = 16 << 20;    // crossover vs one launch per step: profiles/r01_engine_sweep.txt
     env = getenv("XG_ENGINE_MAX_STEP");      // 0: never use the step engine
     if (env) c->engine_max_step = atol(env);
-    {
-        // the engine's grid barrier needs every workgroup resident at once: at most one
-        // per CU by design, never more than the device admits (a partitioned device has
-        // fewer CUs; several ranks per GPU share them)
-        int cus = 0, per_cu = 0;
-        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xgk::step_engine_kernel<16>, xgk::kThreads, 0));
-        c->engine_occ = cus * (per_cu < 1 ? 1 : per_cu);
-        c->engine_wmax = cus;
-        if (c->engine_wmax > c->engine_occ) c->engine_wmax = c->engine_occ;
-        if (c->engine_wmax < 1) c->engine_wmax = 1;
-    }
     env = getenv("XG_ENGINE_DRAIN");         // "1": drain every step even without a hazard
     c->engine_drain = env && !strcmp(env, "1");
     env = getenv("XG_ENGINE_SOLO");          // "0": never solo (the grid engine runs every segment)
     c->solo = !(env && !strcmp(env, "0"));
-    // one solo launch moves <= 1 GiB (2048 pieces per one-wave rail of 512; the wide
-    // descriptors have no window below that): the Theta-scale runs split into 8 launches
-    // instead of 32, 5-6 % faster (profiles/r02/theta/theta_probe_solo_max.txt)
-    c->solo_max = (int64_t)1 << 30;
     env = getenv("XG_ENGINE_SOLO_MAX");
     if (env) c->solo_max = atol(env);
     env = getenv("XG_SOLO_WAVES");           // waves per rail: 1 (default) or 16
@@ -257,22 +244,15 @@ static int init_ctx(xg_ctx *c, const void *uid)
     env = getenv("XG_SOLO_RAILS");
     if (env && atoi(env) > 0) c->solo_rails = std::min(atoi(env), xgk::kSoloMaxRails);
     env = getenv("XG_COPY_LAUNCH_MAX");      // bytes; 0 = one launch however large
-    c->launch_max = env ? atoll(env) : (int64_t)512 << 20;
+    if (env) c->launch_max = atoll(env);
     {
-        int cus = 0;
-        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-        c->rules.cus = cus > 0 ? cus : 256;
         // the wave-persistent copy for the launches of cross-GPU steps (packs, unpacks, the
         // local part): profiles/r03/wave_copy/ -- one GPU's configs[2] pack launch 5.8 ->
         // 6.25 TB/s; the 448 MiB non-temporal launches stay copy_kernel_g (6.0 vs 5.5-5.8);
         // above kWaveMax the one-piece-per-workgroup launch is as fast or faster
         // (profiles/r03/wave_local/: 28 MiB 9.3 vs 9.9 us, 56 MiB 18.7 vs 18.2, 112 MiB equal)
         env = getenv("XG_COPY_WAVE_MIN");     // test hook: 0 puts every cross-GPU launch on the wave copy
-        c->rules.wave_min = env ? atoll(env) : (int64_t)1 << 20;
-        int per_cu = 0;
-        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, xgk::copy_kernel_w<xgk::kWaveKiB>, xgk::kThreads,
-                                                            0));
-        c->wave_grid = c->rules.cus * (per_cu < 1 ? 1 : per_cu);
+        if (env) c->rules.wave_min = atoll(env);
         // test hook: a positive value caps the grid (never raises it), so that a wave gets several
         // pieces -- on a whole device every launch of <= kWaveMax bytes has one piece per wave
         env = getenv("XG_WAVE_GRID");
@@ -294,9 +274,9 @@ static int init_ctx(xg_ctx *c, const void *uid)
     // README configuration as a virtual 8-GPU job (profiles/r03/hybrid/): m6 direct 49 -> 2
     // launches per run, m12 46 -> 6; configs[1..4]'s bulk local parts (MiBs) stay split
     env = getenv("XG_SPLIT_MIN");            // bytes: a smaller local part is not split off
-    c->split_min = env ? atoll(env) : (int64_t)1 << 20;
+    if (env) c->split_min = atoll(env);
     env = getenv("XG_SELF_MAX");             // bytes: local part posted as self send/recv (0: never)
-    c->self_max = env ? atoll(env) : (int64_t)256 << 10;
+    if (env) c->self_max = atoll(env);
     env = getenv("XG_FUSE_STAGE");           // "0": stage copies always in a launch of their own
     c->fuse_stage = !(env && !strcmp(env, "0"));
     env = getenv("XG_SPLIT_AFTER_PACK");     // "0": a split step's local part and its packs start together

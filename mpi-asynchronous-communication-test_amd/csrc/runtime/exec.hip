@@ -45,10 +45,7 @@ double mark_elapsed(const xg_plan *p, int i, const std::vector<unsigned long lon
 // Copy launches.  What a launch is -- its pieces, its ONE kernel kind (PIECE copy_kernel_g<4>,
 // WAVE copy_kernel_w<2 / 4 / 8>, SHIFT copy_kernel_s, EXTENT copy_kernel_x, SMALL copy_kernel_q<1 /
 // 2>; all but WAVE plain or non-temporal), its dispatches, its stream, the mark behind it -- was
-// decided when the plan was loaded (CopyLaunch, plan_load.hip); here the table is walked.
-
-// workgroups (4 waves each) of a copy_kernel_w dispatch over n pieces
-static int wave_wgs(const xg_plan *p, int n) { return std::max(1, std::min(p->ctx->wave_grid, (n + 3) / 4)); }
+// decided when the plan was loaded (CopyLaunch, host/plan_tables.h); here the table is walked.
 
 // One dispatch of launch l: pieces [b, b + n) (SMALL: workgroups [b, b + n)), on the kernel of its
 // kind.  The one exception: only the first dispatch of a cut WAVE launch runs copy_kernel_w; the
@@ -173,43 +170,6 @@ int enqueue_post(xg_plan *p, int s, hipStream_t stream)
     for (int i = st.l_b; i < st.l_rccl; ++i)
         if (p->launches[i].side) HIPCHK(hipStreamWaitEvent(stream, p->join[s], 0));
     return XG_OK;
-}
-
-// The launch-table entries one run issues (a launch of several dispatches counts once) of one
-// kind, XG_COPY_PIECE .. XG_COPY_SMALL.
-extern "C" int xg_plan_kind_launches(const xg_plan *p, int kind)
-{
-    int count = 0;
-    each_launch(p, [&](const CopyLaunch &l) { count += l.kind == kind; });
-    return count;
-}
-
-// The WAVE launches and the geometry launch_one gives their copy_kernel_w dispatch: w workgroups
-// of 4 waves over n pieces.
-extern "C" int xg_plan_wave_launches(const xg_plan *p, int *grid, int *max_pieces_per_wave)
-{
-    int most = 0;
-    each_launch(p, [&](const CopyLaunch &l) {
-        if (l.kind != XG_COPY_WAVE) return;
-        const int m = p->cuts[l.cut + 1] - l.b, w = wave_wgs(p, m);
-        most = std::max(most, (m + 4 * w - 1) / (4 * w));
-    });
-    if (grid) *grid = p->ctx->wave_grid;
-    if (max_pieces_per_wave) *max_pieces_per_wave = most;
-    return xg_plan_kind_launches(p, XG_COPY_WAVE);
-}
-
-extern "C" int xg_plan_shift_launches(const xg_plan *p) { return xg_plan_kind_launches(p, XG_COPY_SHIFT); }
-extern "C" int xg_plan_extent_launches(const xg_plan *p) { return xg_plan_kind_launches(p, XG_COPY_EXTENT); }
-
-// *kib: the SMALL launches' piece size, 0 when there is none; may be NULL
-extern "C" int xg_plan_small_launches(const xg_plan *p, int *kib)
-{
-    if (kib) *kib = 0;
-    each_launch(p, [&](const CopyLaunch &l) {
-        if (kib && l.kind == XG_COPY_SMALL) *kib = l.kib;
-    });
-    return xg_plan_kind_launches(p, XG_COPY_SMALL);
 }
 
 static int enqueue_step(xg_plan *p, int s)

@@ -154,6 +154,157 @@ class CopyChoice(C.Structure):
 COPY_PIECE, COPY_WAVE, COPY_SHIFT, COPY_EXTENT, COPY_SMALL, COPY_NKIND = range(6)   # xg_sched.h XG_COPY_*
 
 
+class PlanKnobs(C.Structure):
+    """xg_plan_knobs: every context setting the plan-table builder reads"""
+    _fields_ = ([("rules", CopyRules)] +
+                [(k, C.c_int64) for k in ("extent_tile", "engine_max_step", "solo_max", "launch_max", "split_min",
+                                          "self_max")] +
+                [(k, C.c_int32) for k in ("variant", "engine_wmax", "engine_drain", "solo", "solo_rails", "solo_waves",
+                                          "wave_grid", "step_chain", "engine_arm", "fuse_stage", "split_after_pack",
+                                          "rank", "nranks", "virt")])
+
+
+class PlanTables:
+    """The tables xg_plan_load builds from a device plan, built with no GPU (xg_plan_tables_build,
+    csrc/host/plan_tables.cc).  dp: a DevPlan (or a pointer to one); base / nbytes: the regions'
+    addresses and sizes (default: 2 MiB-aligned fake addresses, the plan's own region sizes);
+    cus / engine_occ / wave_grid: the device facts xg_init queries (default: a whole MI355X);
+    knobs: xg_plan_knobs or xg_copy_rules fields by name, over xg_plan_knobs_default."""
+    _lib = None
+
+    @classmethod
+    def lib(cls):
+        if cls._lib is None:        # bound at first use: a libxghost without plan_tables.cc still serves the rest
+            h = host()
+            T, I = C.c_void_p, C.POINTER(C.c_int)
+            h.xg_plan_knobs_default.restype = None
+            h.xg_plan_knobs_default.argtypes = [C.POINTER(PlanKnobs), C.c_int, C.c_int, C.c_int]
+            h.xg_plan_tables_build.argtypes = [C.POINTER(DevPlan), C.POINTER(PlanKnobs), C.POINTER(C.c_uint64),
+                                               C.POINTER(C.c_int64), C.POINTER(T)]
+            h.xg_plan_tables_free.restype = None
+            h.xg_plan_tables_free.argtypes = [T]
+            for fn in ("nsteps", "launches", "shift_launches", "extent_launches", "engine", "engine_rails"):
+                getattr(h, "xg_plan_tables_" + fn).argtypes = [T]
+            h.xg_plan_tables_step_form.argtypes = [T, C.c_int]
+            h.xg_plan_tables_kind_launches.argtypes = [T, C.c_int]
+            h.xg_plan_tables_wave_launches.argtypes = [T, I, I]
+            h.xg_plan_tables_small_launches.argtypes = [T, I]
+            h.xg_plan_tables_engine_steps.argtypes = [T, I, I]
+            h.xg_plan_tables_dump.restype = C.c_int64
+            h.xg_plan_tables_dump.argtypes = [T, C.c_char_p, C.c_int64]
+            cls._lib = h
+        return cls._lib
+
+    @classmethod
+    def knobs(cls, cus=256, engine_occ=256, wave_grid=2048, **over):
+        k = PlanKnobs()
+        cls.lib().xg_plan_knobs_default(C.byref(k), cus, engine_occ, wave_grid)
+        rules = set(f[0] for f in CopyRules._fields_)
+        for name, v in over.items():
+            setattr(k.rules if name in rules else k, name, v)      # an unknown name raises (ctypes structures take no new fields)
+            assert name in rules or name in set(f[0] for f in PlanKnobs._fields_), name
+        return k
+
+    def __init__(self, dp, base=None, nbytes=None, cus=256, engine_occ=256, wave_grid=2048, **knobs):
+        h = self.lib()
+        dpp = dp if isinstance(dp, C.POINTER(DevPlan)) else C.pointer(dp)
+        self.base = list(base) if base is not None else [(b + 1) << 40 for b in range(NBUF)]
+        self.nbytes = list(nbytes) if nbytes is not None else list(dpp.contents.region_bytes)
+        self.h = C.c_void_p()
+        k = self.knobs(cus, engine_occ, wave_grid, **knobs)
+        rc = h.xg_plan_tables_build(dpp, C.byref(k), (C.c_uint64 * NBUF)(*self.base), (C.c_int64 * NBUF)(*self.nbytes),
+                                    C.byref(self.h))
+        if rc:
+            raise XGError("xg_plan_tables_build: %d" % rc)
+
+    def close(self):
+        if self.h:
+            self.lib().xg_plan_tables_free(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    def nsteps(self):
+        return self.lib().xg_plan_tables_nsteps(self.h)
+
+    def launches(self):
+        return self.lib().xg_plan_tables_launches(self.h)
+
+    def step_form(self, s):
+        return self.lib().xg_plan_tables_step_form(self.h, s)
+
+    def kind_launches(self):
+        return [self.lib().xg_plan_tables_kind_launches(self.h, k) for k in range(COPY_NKIND)]
+
+    def engine_rails(self):
+        return self.lib().xg_plan_tables_engine_rails(self.h)
+
+    def engine(self):
+        return self.lib().xg_plan_tables_engine(self.h)
+
+    def engine_steps(self):
+        """-> (steps inside segments, segments, hazard barriers)"""
+        ns, nh = C.c_int(), C.c_int()
+        n = self.lib().xg_plan_tables_engine_steps(self.h, C.byref(ns), C.byref(nh))
+        return n, ns.value, nh.value
+
+    def dump(self):
+        return dump_tables(self.h)
+
+    def records(self):
+        return parse_tables(self.dump())
+
+
+def dump_tables(handle):
+    """xg_plan_tables_dump of a handle (a PlanTables', or xg_plan_tables_of a loaded plan)"""
+    h = PlanTables.lib()
+    n = h.xg_plan_tables_dump(handle, None, 0)
+    buf = C.create_string_buffer(n + 1)
+    h.xg_plan_tables_dump(handle, buf, n + 1)
+    return buf.value.decode()
+
+
+def parse_tables(text):
+    """the dump by record tag: {"piece": [[fields...], ...], ...}.  A field that is a number is an
+    int; a pointer "b+off" is the pair (b, off); a record's tag and index are dropped; of
+    "name value" records (plan, step, launch, seg) the result is a dict."""
+    def val(x):
+        if "+" in x and x[0] != "?":
+            b, o = x.split("+")
+            return (int(b), int(o))
+        try:
+            return int(x, 0)
+        except ValueError:
+            return x
+    out = {}
+    for line in text.splitlines():
+        f = line.split()
+        tag = f[0]
+        if tag == "plan":
+            out["plan"] = dict((f[i], val(f[i + 1])) for i in range(1, len(f), 2))
+        elif tag == "step":
+            names = ("stage", "local", "pack", "post", "calls", "bytes", "l")
+            d, i = {}, 2
+            while i < len(f):
+                width = 2 if f[i] in names[:5] else 4 if f[i] == "bytes" else 3 if f[i] == "l" else 1
+                v = [val(x) for x in f[i + 1:i + 1 + width]]
+                d[f[i]] = v[0] if width == 1 else v
+                i += 1 + width
+            out.setdefault("step", []).append(d)
+        elif tag in ("launch", "seg", "call", "fix"):
+            d, i = {}, 2
+            while i < len(f):
+                width = 5 if f[i] == "q" else 2 if f[i] == "steps" else 1
+                v = [val(x) for x in f[i + 1:i + 1 + width]]
+                d[f[i]] = v[0] if width == 1 else v
+                i += 1 + width
+            out.setdefault(tag, []).append(d)
+        else:
+            v = [val(x) for x in f[2:]]
+            out.setdefault(tag, []).append(v[0] if len(v) == 1 else v)
+    return out
+
+
 class RunOpts(C.Structure):
     """xg_run_opts"""
     _fields_ = [("verify", C.c_int), ("fingerprint", C.c_int), ("eager_limit", C.c_int64),

@@ -1,5 +1,5 @@
 #!/bin/bash
-# The launch table (runtime/plan_load.hip: build_tables) against the commit before it.
+# The launch table (host/plan_tables.cc: TableBuilder) against the commit before it.
 #   trace: profiles/launch_table_trace.py under rocprofv3 --kernel-trace, one fresh process per
 #          build, reduced by launch_table_reduce.py to one line per plan (a hash of its ordered
 #          dispatches) and diffed; the sequences themselves (*.full.txt) stay only if they differ

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """The plans whose kernel dispatches pin down how a step's copies launch: every launch form of
-the per-plan launch table (runtime/plan_load.hip: build_tables) -- stage launches alone and
+the per-plan launch table (host/plan_tables.cc: TableBuilder) -- stage launches alone and
 fused, local + pack launches, fused unpack + pack launches, deferred unpacks, split steps in
 both fork orders, the local part inside the RCCL group, wave launches, cut launches, chains.
 Each plan is loaded and run once and every slot is checked against the oracle.

@@ -141,7 +141,7 @@ def window_plan(form, rails_max):
 
 
 def _split_pays(nbytes, n, ncut, gran):
-    """plan_load.hip build_segments' inequality for consecutive solo launches, mirrored only to
+    """plan_tables.cc build_segments' inequality for consecutive solo launches, mirrored only to
     SIZE the plan (10 % kept in hand); the asserted segment and rail counts are the check"""
     traffic = 2.0 * nbytes
     return 1.1 * (ncut * 6e-6 + traffic / (6e12 * gran / 16.0) + n * 0.05e-6) < traffic / 5e12 + n * 1.0e-6

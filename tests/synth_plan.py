@@ -136,7 +136,7 @@ SOLO_LENS = {
 
 
 def _solo_pays(nbytes, n, rails, waves, busy, gran):
-    """plan_load.hip solo_pays, mirrored only to SIZE plans (10 % kept in hand on the rail side):
+    """plan_tables.cc solo_pays, mirrored only to SIZE plans (10 % kept in hand on the rail side):
     the rail count a GPU test asserts is the check that the library's model agreed"""
     traffic = 2.0 * nbytes
     if waves == 1:

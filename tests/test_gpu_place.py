@@ -1,5 +1,5 @@
 """GPU: placement by offset-length lists -- copy_kernel_x (the extent copy of csrc/kernels.h), its
-routing and tile tables (runtime/plan_load.hip), and xg_exchange_w.
+routing and tile tables (host/plan_tables.cc), and xg_exchange_w.
 
 The kernel is driven through synthetic one-step plans with XG_DP_RAGGED | XG_DP_EXTENTS
 (synth_plan's layout: seeded random SEND, poisoned RECV, a poisoned gap around every destination
@@ -23,7 +23,7 @@ from synth_plan import CHUNK_A, Synth, _assert_gaps, _compare, _ctx_env, _layout
 
 pytestmark = pytest.mark.gpu
 
-MEAN_MAX = 1024                 # kExtMeanMax (runtime/rt.h): the routing threshold
+MEAN_MAX = 1024                 # kExtMeanMax (host/plan_tables.h): the routing threshold
 PHASE_LENS = list(range(1, 50)) + [63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097]
 
 

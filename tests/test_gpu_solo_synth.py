@@ -11,7 +11,7 @@ routing as well -- the rail count, the segment count, units above workgroups -- 
 alone would also be right on the other engine, and the step stamps of every run (ordered, inside
 the wall time: a rail with nothing in a step carries its previous stamp, xg_solo_reduce_stamps).
 
-Which engine a segment takes is decided at plan load by a cost model (plan_load.hip solo_pays);
+Which engine a segment takes is decided at plan load by a cost model (plan_tables.cc solo_pays);
 synth_plan._solo_pays mirrors it only to SIZE the plans -- steps that move nothing are added until
 the model prefers rails -- and the asserted rail count is the check that it did.  What the plans
 are (granules, row counts, flags) is checked without a GPU in test_synth_plan.py.

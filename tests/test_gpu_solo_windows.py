@@ -7,7 +7,7 @@ runs on rails stays below bit 18 of those fields; the plans here (sparse_synth.p
 tops -- hulls of exactly 2^28 B packed and 2^32 B wide at granule 1, just over 8 and 32 GiB at
 granules 4 and 16 (bit 31 of a granule offset, scaled by 4 and 16 in 64 bits) -- with 1 KiB
 pieces, the length field's own top bit, behind step barriers, and split_steps goes one granule
-past the window, where plan_load.hip solo_split must cut the run and give each part bases of
+past the window, where plan_tables.cc solo_split must cut the run and give each part bases of
 its own.  The regions are address space: a few hundred KiB move.  SparseSynth judges every byte
 of RECV all the same: the destinations with 4 KiB on both sides byte for byte against numpy, the
 rest by device checksums of 1 MiB spans against the poison's, SEND by checksums before and
