@@ -206,7 +206,13 @@ int xg_plan_small_launches(const xg_plan *p, int *kib);
  * translate of mpi_test.c:233-302).  out == NULL: returns their number. */
 int xg_plan_displs(const xg_plan *p, int64_t *out, int n);
 /* plans[g] = GPU g's plan of one virtual job (xg_init_virtual, g = 0..n-1, same
- * schedule); step_done[nsteps]: device seconds from start to the end of each step. */
+ * schedule); step_done[nsteps]: device seconds from start to the end of each step, from GPU
+ * 0's marks (xg_sched.h xg_step_times).  An engine segment of GPU 0 is ONE launch at its first
+ * step, and the marks of all its steps are enqueued behind it -- by themselves they would put
+ * every step of the segment at the segment's end.  So the segment's time is shared out by GPU
+ * 0's engine stamps, anchored at the mark behind the segment's last step (always marked), as
+ * xg_plan_run does: inside the segment the differences between step times are GPU 0's engine's;
+ * the segment's first step also carries what the other GPUs launched behind it. */
 int xg_vplans_run(xg_plan *const *plans, int n, double *step_done);
 /* Same, with every send/recv pair moved by RCCL: a 1-rank communicator on the
  * device, one ncclGroupStart/End of self ncclSend + ncclRecv per step (matched

@@ -383,6 +383,41 @@ int xg_solo_tables_g(const xg_span *xfer, const int *step_begin, int nsteps, int
 /* Step times of a solo segment [s0, s1) from its rails' stamps (stamps[r * stride + t], 0 =
  * the rail closed nothing there): out[t] = max over rails of the rail's latest stamp <= t. */
 void xg_solo_reduce_stamps(const uint64_t *stamps, int rails, int64_t stride, int s0, int s1, uint64_t *out);
+/* last[rails]: each rail's last step with pieces under the deal of xg_solo_tables_g (-1: none). */
+int xg_solo_rail_last(const xg_span *xfer, const int *step_begin, int nsteps, int rails, int32_t *last);
+/* Before the reduction: the kernel writes a rail's closing stamp to EVERY step behind the rail's
+ * last barrier, which closes the last step but one it has pieces in.  In the steps between that
+ * one and last[r] the rail had nothing: their stamps are zeroed here, so that the reduction carries
+ * the rail's previous stamp (else the time of a heavy last step lands on the first step some rail
+ * sat out before it).  cstep: the tables' [rails][n] closed steps of a segment of n steps whose
+ * first step's stamp is stamps[r * stride + s0]. */
+void xg_solo_carry_tail(uint64_t *stamps, int rails, int64_t stride, int s0, int n, const int *cstep,
+                        const int32_t *last);
+/* step_done[nsteps], seconds from a run's start, from the wall-clock stamps it left (ticks of
+ * wall_hz; every difference is taken in 64 bits, so a wrapped counter is harmless).  The one
+ * place where stamps become times: xg_plan_run, its armed form and xg_vplans_run all call it.
+ *   marks[nsteps + 1]     marks[0] the start's mark, marks[s + 1] the mark behind step s
+ *   chain_stamps[nsteps]  step t's stamp, written by the first workgroup of launch t + 1 (the
+ *                         chain's last by a clock kernel); NULL: the run stamped no chain
+ *   engine_stamps[nsteps] the engine's stamp of step t (solo segments already reduced over their
+ *                         rails, xg_solo_reduce_stamps); NULL: a plan without segments
+ *   seg_of[nsteps], seg_end[]   step s's engine segment (-1: none), and each segment's end s1
+ *   chain_end[nsteps]     != 0 at a chain's first step: the chain's end; NULL: no chains
+ *   need_mark[nsteps]     != 0: a step outside segments and chains was marked; NULL: all were
+ * A chain [s, ce) is anchored at marks[ce], a segment [s, e) at marks[e], both BACKWARDS:
+ * step_done[t] = end - (stamp[last] - stamp[t]) / wall_hz, the last step's = end; a time that
+ * would fall before the run's start is reported as 0.  A marked step outside both ends at its
+ * mark; one that was not marked when the next marked step does (no Timer reads it, and the last
+ * step is always marked).  host_total >= 0 (an armed run, xg.h XG_ENGINE_ARM): ONE segment
+ * covers every step and is anchored at host_total, the host-measured seconds from the ring to
+ * the engine's completion; the marks and the tables may then be NULL.  host_total < 0: none.
+ * What a time means: an engine stamp before its segment's last is an ISSUE time (the step's
+ * loads are over, its stores may still land); a segment's last stamp, a chain stamp (the next
+ * launch starts when the step's own has ended) and a mark are DELIVERED times.
+ * Returns 0 (also for nsteps == 0, whatever the pointers) or XG_EARG. */
+int xg_step_times(int nsteps, const uint64_t *marks, const uint64_t *chain_stamps, const uint64_t *engine_stamps,
+                  const int32_t *seg_of, const int32_t *seg_end, const int32_t *chain_end, const uint8_t *need_mark,
+                  double wall_hz, double host_total, double *step_done);
 
 /* Piece (= workgroup) size of one copy launch over copies of lengths lens[n]: among chunk,
  * chunk/2, ... >= 4 KiB (16-B multiples), the one whose busiest CU -- ceil(pieces / cus)

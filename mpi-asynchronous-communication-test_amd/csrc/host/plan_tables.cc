@@ -232,6 +232,8 @@ static int commit_seg(PlanTables *p, const PlanKnobs *c, SegCand &k, bool solo)
                              reinterpret_cast<uint64_t *>(p->solo_desc.data()) + g.u0, meta.data()) != XG_OK)
             return XG_EARG;
         sb.insert(sb.end(), meta.begin(), meta.end());
+        g.rail_last.resize(k.sh.rails);
+        if (xg_solo_rail_last(k.spans.data(), k.tb.data(), n, k.sh.rails, g.rail_last.data()) != XG_OK) return XG_EARG;
     } else {
         // grid units: the step's transfers cut to B * 4 KiB, one burst of B 16-B loads per lane
         const int64_t unit = (int64_t)g.b * xgk::kThreads * 16;

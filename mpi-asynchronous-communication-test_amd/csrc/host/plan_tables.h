@@ -92,6 +92,7 @@ struct EngSeg {
     const uint8_t *sbase;          // solo: base pointers of the descriptors' offsets
     uint8_t *dbase;
     int64_t bytes;                 // bytes copied per run
+    std::vector<int32_t> rail_last;   // solo: per rail, its last step with pieces (from s0; xg_solo_rail_last)
 };
 
 // The staging displacements of the packed segments (alltoallw translate,

@@ -148,3 +148,96 @@ void xg_solo_reduce_stamps(const uint64_t *stamps, int rails, int64_t stride, in
         }
     }
 }
+
+/* Each rail's last step with pieces, by the deal of xg_solo_tables_g (every piece of every step
+ * in order, round-robin over the rails); -1 for a rail without pieces. */
+int xg_solo_rail_last(const xg_span *xfer, const int *step_begin, int nsteps, int rails, int32_t *last)
+{
+    if (!xfer || !step_begin || !last || nsteps < 1 || rails < 1) return XG_EARG;
+    for (int q = 0; q < rails; ++q) last[q] = -1;
+    int cur = 0;
+    for (int t = 0; t < nsteps; ++t)
+        for (int i = step_begin[t]; i < step_begin[t + 1]; ++i)
+            for (uint64_t o = 0; o < xfer[i].len; o += XG_SOLO_PIECE) {
+                last[cur] = t;
+                cur = (cur + 1) % rails;
+            }
+    return XG_OK;
+}
+
+/* The kernel writes a rail's closing stamp -- taken when its last piece is delivered -- to every
+ * step behind the rail's last barrier.  That barrier closes the last step but one the rail has
+ * pieces in, last[r] being the last; in the steps between the two the rail had nothing, and its time for
+ * them is its previous stamp, not the end of its last step: zero them (0 = closed nothing, which
+ * xg_solo_reduce_stamps carries over).  Otherwise the time of a heavy last step lands on the first
+ * step that some rail sat out before it.  cstep: the tables' [rails][n] closed steps (-1 past the
+ * last); stamps[r * stride + s0 + t] is rail r's stamp of the segment's step t < n. */
+void xg_solo_carry_tail(uint64_t *stamps, int rails, int64_t stride, int s0, int n, const int *cstep,
+                        const int32_t *last)
+{
+    for (int r = 0; r < rails; ++r) {
+        int s_end = 0;
+        for (int k = 0; k < n && cstep[(int64_t)r * n + k] >= 0; ++k) s_end = cstep[(int64_t)r * n + k] + 1;
+        for (int t = s_end; t < last[r] && t < n; ++t) stamps[(int64_t)r * stride + s0 + t] = 0;
+    }
+}
+
+/* Step times from stamps (xg_sched.h): the one place where marks, chain stamps and engine
+ * stamps become step_done[]. */
+static double ticks_before(const uint64_t *st, int last, int t, double wall_hz)
+{
+    return (double)(st[last] - st[t]) / wall_hz;      /* 64-bit difference: wrap-safe */
+}
+
+int xg_step_times(int nsteps, const uint64_t *marks, const uint64_t *chain_stamps, const uint64_t *engine_stamps,
+                  const int32_t *seg_of, const int32_t *seg_end, const int32_t *chain_end, const uint8_t *need_mark,
+                  double wall_hz, double host_total, double *step_done)
+{
+    if (nsteps == 0) return XG_OK;                      /* a plan without steps (its tables may all be NULL) */
+    if (nsteps < 0 || !step_done || !(wall_hz > 0) || (host_total < 0 && (!marks || !seg_of))) return XG_EARG;
+    if (host_total >= 0) {
+        /* an armed run: one segment over every step, anchored at the host-measured end */
+        if (!engine_stamps) return XG_EARG;
+        for (int s = 0; s < nsteps; ++s) {
+            const double x = host_total - ticks_before(engine_stamps, nsteps - 1, s, wall_hz);
+            step_done[s] = s == nsteps - 1 ? host_total : (x > 0 ? x : 0);
+        }
+        return 0;
+    }
+    for (int s = 0; s < nsteps;) {
+        const int gi = seg_of[s];
+        if (chain_stamps && chain_end && chain_end[s]) {
+            /* a chain: launch t + 1 stamped step t's completion, a clock kernel the last one's;
+             * the mark behind it anchors them all */
+            const int ce = chain_end[s];
+            if (ce <= s || ce > nsteps) return XG_EARG;
+            const double end = (double)(marks[ce] - marks[0]) / wall_hz;
+            for (int t = s; t < ce; ++t) {
+                const double x = end - ticks_before(chain_stamps, ce - 1, t, wall_hz);
+                step_done[t] = t == ce - 1 ? end : (x > 0 ? x : 0);
+            }
+            s = ce;
+            continue;
+        }
+        const int e = gi >= 0 ? seg_end[gi] : s + 1;
+        if (e <= s || e > nsteps || (gi >= 0 && !engine_stamps)) return XG_EARG;
+        if (gi < 0 && need_mark && !need_mark[s]) {     /* not marked: the next marked step's time (below) */
+            step_done[s] = -1;
+            s = e;
+            continue;
+        }
+        const double end = (double)(marks[e] - marks[0]) / wall_hz;
+        /* inside a segment: the wall-clock stamps, anchored at the mark after its launch
+         * (the last step of a segment is drained, so its stamp is a delivered time) */
+        for (int t = s; t < e; ++t) {
+            const double x = end - (gi >= 0 ? ticks_before(engine_stamps, e - 1, t, wall_hz) : 0);
+            step_done[t] = t == e - 1 ? end : (x > 0 ? x : 0);
+        }
+        s = e;
+    }
+    /* an unmarked step is reported as done when the next marked one is: no Timer reads it
+     * (xg_sched_timed_steps), and the last step is always marked */
+    for (int s = nsteps - 2; s >= 0; --s)
+        if (step_done[s] < 0) step_done[s] = step_done[s + 1];
+    return 0;
+}

@@ -176,7 +176,7 @@ static void warn_folded_knobs()
     static const char *const folded[] = {
         // round 4: settled tuning
         "XG_COPY_BALANCE", "XG_COPY_CHUNK", "XG_COPY_NT_MIN", "XG_COPY_NT_STREAM", "XG_COPY_WAVE",
-        "XG_COPY_WAVE_MAX", "XG_COPY_WG_COST", "XG_ENGINE_WG", "XG_FUSE_UNPACK", "XG_GRID_CACHE_MAX",
+        "XG_COPY_WAVE_MAX", "XG_COPY_WG_COST", "XG_FUSE_UNPACK", "XG_GRID_CACHE_MAX",
         "XG_PIECE_ORDER", "XG_SOLO_MIN_STEPS", "XG_SOLO_RELAY", "XG_SPLIT_LOCAL",
         // round 5: environment twins of bin/test options (--fingerprint, --eager-limit, ...)
         "XG_FINGERPRINT", "XG_EAGER_LIMIT", "XG_PACK_MAX_SEG", "XG_PACK_MIN", "XG_PACK_FORM"};
@@ -231,6 +231,10 @@ static int init_ctx(xg_ctx *c, const void *uid)
     if (env && atoi(env) >= 1 && atoi(env) <= 1024) c->rules.small_order = atoi(env);
     env = getenv("XG_ENGINE_MAX_STEP");      // 0: never use the step engine
     if (env) c->engine_max_step = atol(env);
+    // test hook: a positive value caps the grid engine's workgroups (never raises them), so that a
+    // step's bytes are confined to a known number of CUs
+    env = getenv("XG_ENGINE_WG");
+    if (env && atoi(env) > 0) c->engine_wmax = std::max(1, std::min(c->engine_wmax, atoi(env)));
     env = getenv("XG_ENGINE_DRAIN");         // "1": drain every step even without a hazard
     c->engine_drain = env && !strcmp(env, "1");
     env = getenv("XG_ENGINE_SOLO");          // "0": never solo (the grid engine runs every segment)

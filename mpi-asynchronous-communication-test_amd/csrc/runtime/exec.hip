@@ -253,17 +253,41 @@ int launch_seg(xg_plan *p, const EngSeg &g, hipStream_t stream, bool armed)
 // segments stamp once per step; a solo segment's rails each stamp the steps they
 // closed (0 elsewhere), so a rail's stamp of step t is its latest at or before t
 // and the step's is the MAX over rails
-static int read_stamps(const xg_plan *p, std::vector<unsigned long long> &st)
+int read_stamps(const xg_plan *p, std::vector<unsigned long long> &st)
 {
     const size_t n = (size_t)p->nsteps;
     std::vector<unsigned long long> all(n * p->stamp_rails);
     HIPCHK(hipMemcpy(all.data(), p->d_engine + 1, 8 * all.size(), hipMemcpyDeviceToHost));
     st.assign(all.begin(), all.begin() + n);
     for (const EngSeg &g : p->segs)
-        if (g.solo)
+        if (g.solo) {
+            // a rail's closing stamp stands in every step behind its last barrier: not its time
+            // for the steps it sat out before its last one with pieces (xg_solo_carry_tail)
+            const int *cstep = p->sb.data() + g.sb_off + (size_t)g.w * (g.npieces / g.wv + 1);
+            xg_solo_carry_tail(reinterpret_cast<uint64_t *>(all.data()), g.w, (int64_t)n, g.s0, g.s1 - g.s0, cstep,
+                               g.rail_last.data());
             xg_solo_reduce_stamps(reinterpret_cast<const uint64_t *>(all.data()), g.w, (int64_t)n, g.s0, g.s1,
                                   reinterpret_cast<uint64_t *>(st.data()));
+        }
     return XG_OK;
+}
+
+// step_done[] of a run of p from the stamps read back after it (libxghost, xg_step_times): the
+// marks gs, the chain stamps cst and the engine stamps st (each null when the run has none),
+// under p's segments, chains and step marks; host_total >= 0: an armed run's host-measured time
+int step_times(const xg_plan *p, const std::vector<unsigned long long> *gs, const std::vector<unsigned long long> *cst,
+               const std::vector<unsigned long long> *st, double wall_hz, double host_total, double *step_done)
+{
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "stamps are 64-bit");
+    auto u64 = [](const std::vector<unsigned long long> *v) {
+        return v ? reinterpret_cast<const uint64_t *>(v->data()) : nullptr;
+    };
+    std::vector<int32_t> seg_end;
+    for (const EngSeg &g : p->segs) seg_end.push_back(g.s1);
+    return xg_step_times(p->nsteps, u64(gs), u64(cst), u64(st), p->seg_of.data(), seg_end.data(), p->chain_end.data(),
+                         reinterpret_cast<const uint8_t *>(p->need_mark.data()), wall_hz, host_total, step_done)
+               ? XG_EARG
+               : XG_OK;
 }
 
 // after a synchronised run: did an engine workgroup give up at a grid barrier?
@@ -332,11 +356,7 @@ static int run_armed(xg_plan *p, double *step_done, double *step_post, double *w
     if (step_done) {
         std::vector<unsigned long long> st;
         if ((rc = read_stamps(p, st))) return rc;
-        const double total = t1 - t0;
-        for (int s = 0; s < p->nsteps; ++s) {
-            const double x = total - (double)(st[p->nsteps - 1] - st[s]) / c->wall_hz;
-            step_done[s] = s == p->nsteps - 1 ? total : (x > 0 ? x : 0);
-        }
+        return step_times(p, nullptr, nullptr, &st, c->wall_hz, t1 - t0, step_done);
     }
     return XG_OK;
 }
@@ -459,38 +479,8 @@ extern "C" int xg_plan_run(xg_plan *p, double *step_done, double *step_post, dou
         HIPCHK(hipMemcpy(cst.data(), p->d_cstamp, 8 * (size_t)p->nsteps, hipMemcpyDeviceToHost));
     }
     if ((rc = read_marks(p, gs))) return rc;
-    for (int s = 0; s < p->nsteps;) {
-        const int gi = p->seg_of[s];
-        if (chains && p->chain_end[s]) {
-            const int ce = p->chain_end[s];
-            const double end = mark_elapsed(p, ce - 1, gs);
-            for (int t = s; t < ce; ++t) {
-                const double x = end - (double)(cst[ce - 1] - cst[t]) / c->wall_hz;
-                step_done[t] = t == ce - 1 ? end : (x > 0 ? x : 0);
-            }
-            s = ce;
-            continue;
-        }
-        const int e = gi >= 0 ? p->segs[gi].s1 : s + 1;
-        if (gi < 0 && !p->need_mark[s]) {     // not marked: the next marked step's time (below)
-            step_done[s] = -1;
-            s = e;
-            continue;
-        }
-        const double end = mark_elapsed(p, e - 1, gs);
-        // inside a segment: the wall-clock stamps, anchored at the mark after its launch
-        // (the last step of a segment is drained, so its stamp is a delivered time)
-        for (int t = s; t < e; ++t) {
-            const double x = end - (double)(st.empty() ? 0 : st[e - 1] - st[t]) / c->wall_hz;
-            step_done[t] = t == e - 1 ? end : (x > 0 ? x : 0);
-        }
-        s = e;
-    }
-    // an unmarked step is reported as done when the next marked one is: no Timer reads it
-    // (xg_sched_timed_steps), and the last step is always marked
-    for (int s = p->nsteps - 2; s >= 0; --s)
-        if (step_done[s] < 0) step_done[s] = step_done[s + 1];
-    return XG_OK;
+    // chains and segments anchored backwards at the mark behind them, unmarked steps filled in
+    return step_times(p, &gs, chains ? &cst : nullptr, p->segs.empty() ? nullptr : &st, c->wall_hz, -1.0, step_done);
 }
 
 // Which steps an eager or captured run marks with a clock stamp (need[s] != 0; null: all).

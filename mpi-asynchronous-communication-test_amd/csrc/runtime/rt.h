@@ -246,6 +246,9 @@ struct StdoutToStderr {
 int mark(xg_plan *p, int i, hipStream_t stream);
 int read_marks(const xg_plan *p, std::vector<unsigned long long> &gs);
 double mark_elapsed(const xg_plan *p, int i, const std::vector<unsigned long long> &gs);
+int read_stamps(const xg_plan *p, std::vector<unsigned long long> &st);
+int step_times(const xg_plan *p, const std::vector<unsigned long long> *gs, const std::vector<unsigned long long> *cst,
+               const std::vector<unsigned long long> *st, double wall_hz, double host_total, double *step_done);
 int enqueue_pre(xg_plan *p, int s, hipStream_t stream, hipStream_t side, unsigned long long *start = nullptr);
 int enqueue_post(xg_plan *p, int s, hipStream_t stream);
 int launch_seg(xg_plan *p, const EngSeg &g, hipStream_t stream, bool armed = false);

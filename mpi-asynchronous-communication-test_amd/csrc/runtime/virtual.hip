@@ -112,7 +112,11 @@ static int vplans_run(xg_plan *const *plans, int n, double *step_done, bool rccl
                 if (plans[g]->seg_of[s] < 0 && (rc = enqueue_post(plans[g], s, st))) return rc;
             if (rccl && plans[0]->steps[s].sync_after)
                 NCCLCHK(ncclAllReduce(c0->d_red, c0->d_red, 1, ncclFloat64, ncclMax, c0->comm, st));
-            if (plans[0]->need_mark[s] && (rc = mark(plans[0], s, st))) return rc;   // the job's marks: GPU 0's
+            // the job's marks: GPU 0's, and the end of each of its engine segments (the anchor of
+            // the segment's stamps) whether a Timer reads that step or not
+            const int g0 = plans[0]->seg_of[s];
+            if ((plans[0]->need_mark[s] || (g0 >= 0 && plans[0]->segs[g0].s1 == s + 1)) && (rc = mark(plans[0], s, st)))
+                return rc;
         }
         return XG_OK;
     };
@@ -144,10 +148,14 @@ static int vplans_run(xg_plan *const *plans, int n, double *step_done, bool rccl
     for (int g = 0; g < n; ++g)
         if ((rc = xg_plan_check(plans[g]))) return rc;
     if (step_done) {
-        std::vector<unsigned long long> gs;
+        // GPU 0's marks; inside one of its engine segments -- ONE launch at the segment's first
+        // step, every mark of its steps enqueued behind it -- its engine's stamps share the
+        // segment's time out, anchored at the mark behind the segment's last step as in
+        // xg_plan_run; an unmarked step: done with the next marked one
+        std::vector<unsigned long long> gs, est;
         if ((rc = read_marks(plans[0], gs))) return rc;
-        for (int s = nst - 1; s >= 0; --s)      // an unmarked step: done with the next marked one
-            step_done[s] = plans[0]->need_mark[s] ? mark_elapsed(plans[0], s, gs) : step_done[s + 1];
+        if (!plans[0]->segs.empty() && (rc = read_stamps(plans[0], est))) return rc;
+        return step_times(plans[0], &gs, nullptr, est.empty() ? nullptr : &est, c0->wall_hz, -1.0, step_done);
     }
     return XG_OK;
 }

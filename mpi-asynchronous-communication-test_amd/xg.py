@@ -514,6 +514,54 @@ def solo_reduce_stamps(stamps, s0, s1):
     return list(out)
 
 
+def solo_rail_last(steps, rails):
+    """xg_solo_rail_last over steps = [[(src, dst, len), ...], ...] -> each rail's last step with pieces"""
+    spans = [x for st in steps for x in st]
+    arr = (Span * max(1, len(spans)))(*[Span(*x) for x in spans])
+    beg = [0]
+    for st in steps:
+        beg.append(beg[-1] + len(st))
+    fn = host().xg_solo_rail_last
+    fn.argtypes = [C.POINTER(Span), C.POINTER(C.c_int), C.c_int, C.c_int, C.POINTER(C.c_int32)]
+    out = (C.c_int32 * rails)()
+    rc = fn(arr, (C.c_int * len(beg))(*beg), len(steps), rails, out)
+    if rc:
+        raise XGError("xg_solo_rail_last: %d" % rc)
+    return list(out)
+
+
+def solo_carry_tail(stamps, csteps, last):
+    """xg_solo_carry_tail over stamps = [rail][step] of one segment, csteps = the tables' per-rail
+    closed-step lists, last = xg_solo_rail_last -> the stamps with the sat-out tail steps zeroed"""
+    R, n = len(stamps), len(stamps[0])
+    arr = (C.c_uint64 * (R * n))(*[x for row in stamps for x in row])
+    fn = host().xg_solo_carry_tail
+    fn.restype = None
+    fn.argtypes = [C.POINTER(C.c_uint64), C.c_int, C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int32)]
+    fn(arr, R, n, 0, n, (C.c_int * (R * n))(*[x for row in csteps for x in row]), (C.c_int32 * R)(*last))
+    return [list(arr[r * n:(r + 1) * n]) for r in range(R)]
+
+
+def step_times(marks, seg_of, seg_end, wall_hz, chain_stamps=None, engine_stamps=None, chain_end=None,
+               need_mark=None, host_total=-1.0):
+    """xg_step_times: step_done[] (seconds) from a run's stamps (64-bit ints); marks = [start,
+    boundary 0, ...] (None for an armed run, host_total >= 0), the other lists one entry per step
+    or None -> (rc, step_done)"""
+    n = len(seg_of)
+
+    def arr(t, v):
+        return (t * max(1, len(v)))(*v) if v is not None else None
+    u64, i32 = C.POINTER(C.c_uint64), C.POINTER(C.c_int32)
+    fn = host().xg_step_times
+    fn.argtypes = [C.c_int, u64, u64, u64, i32, i32, i32, C.POINTER(C.c_uint8), C.c_double, C.c_double,
+                   C.POINTER(C.c_double)]
+    out = (C.c_double * max(1, n))()
+    rc = fn(n, arr(C.c_uint64, marks), arr(C.c_uint64, chain_stamps), arr(C.c_uint64, engine_stamps),
+            arr(C.c_int32, seg_of), arr(C.c_int32, seg_end), arr(C.c_int32, chain_end), arr(C.c_uint8, need_mark),
+            wall_hz, host_total, out)
+    return rc, list(out)[:n]
+
+
 def _pairs(n, arr, groups=False):
     if groups:
         return [(q.step, q.group, q.src, q.dst, q.send_call, q.recv_call, q.len) for q in arr[:n]]
