@@ -345,6 +345,45 @@ int xg_exchange_w(xg_ctx *ctx, int method, int procs, int cb_nodes, const xg_ext
                   xg_timer *timers, int iter, int ntimes, const xg_run_opts *opts,
                   int64_t *bad_slots, int64_t *bad_exts, double *place_s, char *err, size_t errlen);
 
+/* ------------------------------------------------------------------ strided placement on the device
+ * One GPU's rows (xg_vec_rows_build, xg_sched.h) as ONE launch of copy_kernel_v: a workgroup per tile
+ * of one row, every block derived by arithmetic (xg_vec_piece_at), no descriptor per block.
+ * xg_vecplace_load builds the launch's tables on the host (xg_vec_tables_build with the context's
+ * extent tile, 256 pieces per tile and its launch_max, XG_COPY_LAUNCH_MAX honoured) over the regions'
+ * addresses and uploads the rows and tile0: XG_EARG, with nothing allocated or launched, for whatever
+ * the builder refuses (a non-positive row, a block outside its region, too many tiles).  The regions
+ * must outlive the object.  xg_vecplace_run enqueues a start mark, one dispatch per cut pair and an
+ * end mark on the context's stream, waits, and returns the device seconds between the marks
+ * (device_seconds may be NULL); non-temporal by the context's copy variant, by size as a placement
+ * plan's launch when that is 0.  xg_vecplace_tiles / _dispatches: the launch's workgroups and kernel
+ * dispatches (0 for an empty list). */
+typedef struct xg_vecplace xg_vecplace;
+int xg_vecplace_load(xg_ctx *ctx, xg_regions *r, const xg_vrow *rows, int64_t n, xg_vecplace **out);
+int xg_vecplace_run(xg_vecplace *v, double *device_seconds);
+int xg_vecplace_free(xg_vecplace *v);
+int64_t xg_vecplace_tiles(const xg_vecplace *v);
+int xg_vecplace_dispatches(const xg_vecplace *v);
+
+/* xg_exchange_w with the placement described by STRIDED RUNS (exchange_wv.c; the list rules,
+ * xg_vecs_check and xg_vecs_expand: xg_sched.h): what xg_exchange_w does for xg_vecs_expand of the
+ * list, byte for byte, without ever building that expansion -- the list is judged by xg_vecs_check,
+ * the pair lengths are xg_vecs_lens', the placement is one copy_kernel_v launch over the GPU's rows
+ * (xg_vec_rows_build, xg_vecplace_load).  send / recv, timers, *bad_slots, *place_s and the error
+ * rules are xg_exchange_w's; a list the checker refuses fails every rank alike with XG_EARG and the
+ * checker's words before the exchange's first RCCL call.  opts->verify: every block of every hosted
+ * row is compared on both sides of the placement by xg_chk_spans, at most 65536 spans a launch
+ * (host memory stays bounded whatever the counts); *bad_vecs counts the rows with a differing block.
+ * Routing: a GPU whose hosted rows have a mean block length above 1024 B (kVecLenMax; few, long
+ * extents), or any list with XG_VEC_COPY=0, is placed as before -- xg_vecs_expand into
+ * xg_exchange_w; the ranks settle this together (one MAX all-reduce), so that all of them take the
+ * same road.  xg_exchange_wv_tiles: the copy_kernel_v workgroups of this process's last
+ * xg_exchange_wv placement (0 when it went by the expansion). */
+int xg_exchange_wv(xg_ctx *ctx, int method, int procs, int cb_nodes, const xg_vec *v, int64_t n,
+                   const int64_t *dom_bytes, const int *rank_list, int comm_size, void *send, void *recv,
+                   xg_timer *timers, int iter, int ntimes, const xg_run_opts *opts,
+                   int64_t *bad_slots, int64_t *bad_vecs, double *place_s, char *err, size_t errlen);
+int64_t xg_exchange_wv_tiles(void);
+
 /* The operators under the reference's names (mpi_test.c line of the original). */
 #define XG_METHOD_DECL(name)                                                                     \
     int name(xg_ctx *ctx, int procs, int cb_nodes, int data_size, int *rank_list, int comm_size, \

@@ -602,7 +602,7 @@ int xg_vecs_lens(const xg_vec *v, int64_t n, int procs, int cb_nodes, int64_t *l
 int xg_vecs_check(const xg_vec *v, int64_t n, int procs, int cb_nodes, const int64_t *dom_bytes, int scatter,
                   char *err, size_t errlen);
 /* One table row of a strided placement -- what a copy kernel that derives every block by arithmetic
- * reads in place of a descriptor per block (only the host half exists: DESIGN.md section 11):
+ * reads in place of a descriptor per block (copy_kernel_v):
  * `count` blocks of `len` bytes, block j from src_off + j * src_step of region src_buf to
  * dst_off + j * dst_step of region dst_buf. */
 typedef struct { int32_t src_buf, dst_buf; int64_t src_off, dst_off, src_step, dst_step, len, count; } xg_vrow;
@@ -764,6 +764,38 @@ int xg_plan_tables_engine_steps(const xg_plan_tables *t, int *nseg, int *nhaz);
 /* Every table as text, one record per line in a fixed order, every pointer as region+offset.
  * Returns the length (without the final NUL); at most cap bytes are written; buf may be NULL. */
 int64_t xg_plan_tables_dump(const xg_plan_tables *t, char *buf, int64_t cap);
+
+/* ---------------------------------------------------------------- row launch tables (vec_tables.cc)
+ * What xg_vecplace_load (xg.h) makes of GPU g's xg_vrow list before it touches the device: everything
+ * one copy_kernel_v launch reads, as host arithmetic over the rows and the regions' bases and sizes.
+ *   device rows  {src, dst, src_step, dst_step, len, count} per row, the pointers absolute;
+ *   tile0        rows + 1 entries, the prefix of xg_vec_row_tiles (xg_vec_rows_tiles);
+ *   cuts         the launch's dispatches, as tile indices from 0: dispatch k runs tiles
+ *                [cut k, cut k + 1).  A launch of more than 1.5 x launch_max bytes goes as dispatches
+ *                of about launch_max bytes of whole tiles (launch_max <= each < launch_max + its last
+ *                tile's bytes; a cut may fall inside a row), and no runt closes it: a remainder of
+ *                fewer than 16 tiles or less than launch_max / 2 bytes joins the dispatch before it.
+ *                launch_max == 0: one dispatch.  O(rows + cuts) time, whatever the rows' counts.
+ * XG_EARG with a message on stderr (*out is then NULL) for a row with len <= 0 or count <= 0, a row
+ * whose first or last block leaves its region on either side (in 64 bits; an offset or a byte total
+ * that overflows int64 is refused as such), a region index out of range, more than INT32_MAX tiles,
+ * tile_bytes < 1, tile_pieces outside 1 .. 256 or launch_max < 0.  n == 0 is XG_OK: no tile, no
+ * dispatch.  XG_ENOMEM. */
+typedef struct xg_vec_tables xg_vec_tables;
+int xg_vec_tables_build(const xg_vrow *rows, int64_t n, const uint64_t base[XG_NBUF], const int64_t bytes[XG_NBUF],
+                        int64_t tile_bytes, int tile_pieces, int64_t launch_max, xg_vec_tables **out);
+void xg_vec_tables_free(xg_vec_tables *t);
+int64_t xg_vec_tables_rows(const xg_vec_tables *t);
+int64_t xg_vec_tables_tiles(const xg_vec_tables *t);
+int xg_vec_tables_dispatches(const xg_vec_tables *t);
+int64_t xg_vec_tables_bytes(const xg_vec_tables *t);                    /* the launch's bytes */
+int64_t xg_vec_tables_cut(const xg_vec_tables *t, int k);               /* k in 0 .. dispatches; -1 outside */
+int64_t xg_vec_tables_dispatch_bytes(const xg_vec_tables *t, int k);    /* k in 0 .. dispatches - 1; -1 outside */
+/* Every table as text, one record per line, every pointer as region+offset, in the manner of
+ * xg_plan_tables_dump: "vec rows .. tiles .. dispatches .. bytes .. tile_bytes .. tile_pieces ..
+ * launch_max ..", then "row i src dst src_step dst_step len count", "tile0 i v", "cut i v",
+ * "dbytes i v".  Returns the length (without the final NUL); at most cap bytes are written. */
+int64_t xg_vec_tables_dump(const xg_vec_tables *t, char *buf, int64_t cap);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,16 @@ struct DCopy {          // one workgroup's piece of a transfer (absolute device 
     int64_t len;
 };
 
+// One row of a strided placement (copy_kernel_v; built by host/vec_tables.cc from an xg_vrow):
+// `count` blocks of `len` bytes, block j from src + j * src_step to dst + j * dst_step.  The
+// kernel derives every block from these six numbers (xg_vec_piece_at): no descriptor per block.
+struct DVRow {
+    const uint8_t *src;
+    uint8_t *dst;
+    int64_t src_step, dst_step;
+    int64_t len, count;
+};
+
 // Piece table fix-up after the scan: piece k of a packed copy c moves
 // [o, o + len) of it; its staging side (dst of a pack, src of an unpack) is
 // staging base + disp[c] + o.

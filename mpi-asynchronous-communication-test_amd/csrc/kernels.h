@@ -26,6 +26,9 @@
 //  copy_kernel_x      the copy of a placement plan's short extents: one workgroup per TILE of up to
 //                     256 pieces; a scan of the pieces' 16-B destination cells, one cell per lane,
 //                     two aligned granules funnel-shifted at a per-lane phase.
+//  copy_kernel_v      the same copy for strided runs: one workgroup per tile of one ROW (count blocks
+//                     of len bytes a step apart), every block derived by arithmetic -- no descriptor
+//                     per block; shares copy_kernel_x's scan and sweep (ext_tile_copy).
 //  step_engine_kernel a whole GPU-local run of small steps in one persistent
 //                     launch: bursts per step, grid barrier + wall-clock stamp between.
 //  solo_engine_kernel the same for small plans in ONE workgroup: workgroup barrier
@@ -1327,24 +1330,16 @@ __device__ __forceinline__ void ext_store_cell(uint8_t *cell, u32x4 w, int o0, i
     }
 }
 
-template <bool NT = false>
-__global__ __launch_bounds__(kThreads) void copy_kernel_x(const DCopy *__restrict__ pieces,
-                                                          const int *__restrict__ tile_begin,
-                                                          unsigned long long *start)
+// Steps 2 - 4 for one workgroup, shared by copy_kernel_x and copy_kernel_v: lane tid brings its piece
+// (len bytes from s to d; len == 0: none) however it found it.  Uniform control flow up to the sweep:
+// every lane of the workgroup must call it.
+template <bool NT>
+__device__ __forceinline__ void ext_tile_copy(uint64_t s, uint64_t d, int len)
 {
     __shared__ uint64_t l_src[kThreads], l_dst[kThreads];
     __shared__ int l_len[kThreads], l_cs[kThreads], wsum[kThreads / 64];
-    if (start && blockIdx.x == 0 && threadIdx.x == 0) *start = (unsigned long long)wall_clock64();
     const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tb = tile_begin[blockIdx.x];
-    const int np = tile_begin[blockIdx.x + 1] - tb;          // 1 .. kThreads (the host's tile cap)
-    uint64_t s = 0, d = 0;
-    int len = 0, x0 = 0;
-    if (tid < np) {
-        const DCopy c = pieces[tb + tid];
-        s = (uint64_t)(uintptr_t)c.src; d = (uint64_t)(uintptr_t)c.dst; len = (int)c.len;
-        if (len > 0) x0 = (int)(((d + (uint64_t)len - 1) >> 4) - (d >> 4)) + 1;
-    }
+    const int x0 = len > 0 ? (int)(((d + (uint64_t)len - 1) >> 4) - (d >> 4)) + 1 : 0;
     int x = x0;                                             // inclusive scan inside the wave
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
@@ -1396,6 +1391,62 @@ __global__ __launch_bounds__(kThreads) void copy_kernel_x(const DCopy *__restric
 #pragma unroll
         for (int u = 0; u < kExtU; ++u) ext_store_cell<NT>(cell[u], shift_window(a[u], b[u], ph[u]), o0[u], o1[u]);
     }
+}
+
+template <bool NT = false>
+__global__ __launch_bounds__(kThreads) void copy_kernel_x(const DCopy *__restrict__ pieces,
+                                                          const int *__restrict__ tile_begin,
+                                                          unsigned long long *start)
+{
+    if (start && blockIdx.x == 0 && threadIdx.x == 0) *start = (unsigned long long)wall_clock64();
+    const int tid = (int)threadIdx.x;
+    const int tb = tile_begin[blockIdx.x];
+    const int np = tile_begin[blockIdx.x + 1] - tb;          // 1 .. kThreads (the host's tile cap)
+    uint64_t s = 0, d = 0;
+    int len = 0;
+    if (tid < np) {
+        const DCopy c = pieces[tb + tid];
+        s = (uint64_t)(uintptr_t)c.src; d = (uint64_t)(uintptr_t)c.dst; len = (int)c.len;
+    }
+    ext_tile_copy<NT>(s, d, len);
+}
+
+// ---------------------------------------------------------------- row copy
+// copy_kernel_v<NT>: the same launch of many short blocks when they are the blocks of STRIDED RUNS
+// (xg_vrow: count blocks of len bytes a step apart on either side) -- a regular file view.  There is
+// no descriptor per block anywhere: one workgroup per TILE of one ROW, and
+//   * workgroup base + blockIdx.x finds its row by a binary search over tile0 (the prefix of the
+//     rows' tile counts, rows + 1 entries, strictly increasing: every row has a tile), uniform in
+//     the workgroup -- scalar loads, as span_chk_kernel searches blk0 -- and loads the row's 48-B
+//     record once, uniformly;
+//   * lane i derives its piece of the tile with xg_vec_piece_at (xg_sched.h: the function the host
+//     tests walk), 64-bit offsets and products throughout: block t * bpt + i of the row when blocks
+//     are short, lane 0 alone with piece t of a longer block;
+//   * the pieces are copied by ext_tile_copy: copy_kernel_x's scan and sweep, with its promises --
+//     nothing outside [dst, dst + len) of any block is written, nothing outside the granules of a
+//     block's first and last source byte is read, no scratch, no atomics, no LDS beyond that
+//     function's, plain vector loads and stores only.
+// tile_bytes / tile_pieces: what the host dealt the tiles by (tile_pieces <= kThreads, a piece
+// <= tile_bytes < 2^31).  base: the dispatch's first tile.  start: as copy_kernel_g.
+template <bool NT = false>
+__global__ __launch_bounds__(kThreads) void copy_kernel_v(const DVRow *__restrict__ rows,
+                                                          const int *__restrict__ tile0, int nrows, uint32_t base,
+                                                          int64_t tile_bytes, int tile_pieces,
+                                                          unsigned long long *start)
+{
+    if (start && blockIdx.x == 0 && threadIdx.x == 0) *start = (unsigned long long)wall_clock64();
+    const int t = (int)(base + blockIdx.x);
+    int lo = 0, hi = nrows - 1;                   // the last row with tile0 <= t
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tile0[mid] <= t) lo = mid;
+        else hi = mid - 1;
+    }
+    const DVRow r = rows[lo];
+    const xg_vec_at p = xg_vec_piece_at(0, 0, r.src_step, r.dst_step, r.len, r.count, tile_bytes, tile_pieces,
+                                        (int64_t)(t - tile0[lo]), (int)threadIdx.x);
+    ext_tile_copy<NT>((uint64_t)(uintptr_t)r.src + (uint64_t)p.src_off, (uint64_t)(uintptr_t)r.dst + (uint64_t)p.dst_off,
+                      (int)p.n);
 }
 
 }  // namespace xgk

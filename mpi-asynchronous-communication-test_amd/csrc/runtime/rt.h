@@ -8,6 +8,7 @@
 //                  graph, armed runs
 //   virtual.hip    a whole G-GPU job on one device (test hook)
 //   measure.hip    kernel-timing sessions and the RCCL p2p microbenchmark
+//   vecplace.hip   xg_vecplace_*: a strided placement as one copy_kernel_v launch (host/vec_tables.cc's tables)
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -280,8 +280,8 @@ def parse_tables(text):
     for line in text.splitlines():
         f = line.split()
         tag = f[0]
-        if tag == "plan":
-            out["plan"] = dict((f[i], val(f[i + 1])) for i in range(1, len(f), 2))
+        if tag in ("plan", "vec"):
+            out[tag] = dict((f[i], val(f[i + 1])) for i in range(1, len(f), 2))
         elif tag == "step":
             names = ("stage", "local", "pack", "post", "calls", "bytes", "l")
             d, i = {}, 2
@@ -303,6 +303,88 @@ def parse_tables(text):
             v = [val(x) for x in f[2:]]
             out.setdefault(tag, []).append(v[0] if len(v) == 1 else v)
     return out
+
+
+class VecTables:
+    """The tables xg_vecplace_load builds from a GPU's row list, built with no GPU
+    (xg_vec_tables_build, csrc/host/vec_tables.cc).  rows: VRow records or (src_buf, dst_buf, src_off,
+    dst_off, src_step, dst_step, len, count) tuples; nbytes: the regions' sizes (NBUF entries);
+    base: their addresses (default: fake ones a TiB apart).  XGError when the builder refuses."""
+    _lib = None
+
+    @classmethod
+    def lib(cls):
+        if cls._lib is None:
+            h = host()
+            T, i64 = C.c_void_p, C.c_int64
+            h.xg_vec_tables_build.argtypes = [C.POINTER(VRow), i64, C.POINTER(C.c_uint64), C.POINTER(i64), i64, C.c_int,
+                                              i64, C.POINTER(T)]
+            h.xg_vec_tables_free.restype = None
+            h.xg_vec_tables_free.argtypes = [T]
+            for fn in ("rows", "tiles", "bytes"):
+                getattr(h, "xg_vec_tables_" + fn).restype = i64
+                getattr(h, "xg_vec_tables_" + fn).argtypes = [T]
+            h.xg_vec_tables_dispatches.argtypes = [T]
+            for fn in ("cut", "dispatch_bytes"):
+                getattr(h, "xg_vec_tables_" + fn).restype = i64
+                getattr(h, "xg_vec_tables_" + fn).argtypes = [T, C.c_int]
+            h.xg_vec_tables_dump.restype = i64
+            h.xg_vec_tables_dump.argtypes = [T, C.c_char_p, i64]
+            cls._lib = h
+        return cls._lib
+
+    def __init__(self, rows, nbytes, base=None, tile_bytes=32768, tile_pieces=256, launch_max=512 << 20):
+        h = self.lib()
+        arr, n = _vrow_array(rows)
+        self.base = list(base) if base is not None else [(b + 1) << 40 for b in range(NBUF)]
+        self.nbytes = list(nbytes) + [0] * (NBUF - len(nbytes))
+        self.h = C.c_void_p()
+        rc = h.xg_vec_tables_build(arr, n, (C.c_uint64 * NBUF)(*self.base), (C.c_int64 * NBUF)(*self.nbytes), tile_bytes,
+                                   tile_pieces, launch_max, C.byref(self.h))
+        if rc:
+            raise XGError("xg_vec_tables_build: %d" % rc)
+
+    def close(self):
+        if self.h:
+            self.lib().xg_vec_tables_free(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    @property
+    def rows(self):
+        return self.lib().xg_vec_tables_rows(self.h)
+
+    @property
+    def tiles(self):
+        return self.lib().xg_vec_tables_tiles(self.h)
+
+    @property
+    def dispatches(self):
+        return self.lib().xg_vec_tables_dispatches(self.h)
+
+    @property
+    def bytes(self):
+        return self.lib().xg_vec_tables_bytes(self.h)
+
+    def cuts(self):
+        """the dispatches' tile boundaries: dispatches + 1 entries from 0 to tiles"""
+        return [self.lib().xg_vec_tables_cut(self.h, k) for k in range(self.dispatches + 1)]
+
+    def dispatch_bytes(self):
+        return [self.lib().xg_vec_tables_dispatch_bytes(self.h, k) for k in range(self.dispatches)]
+
+    def dump(self):
+        h = self.lib()
+        n = h.xg_vec_tables_dump(self.h, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        h.xg_vec_tables_dump(self.h, buf, n + 1)
+        return buf.value.decode()
+
+    def records(self):
+        """the dump by record tag, as parse_tables gives a plan's: "vec" a dict, "row" lists of
+        [(buf, off) src, (buf, off) dst, src_step, dst_step, len, count], "tile0" / "cut" / "dbytes" ints"""
+        return parse_tables(self.dump())
 
 
 class RunOpts(C.Structure):
@@ -1122,6 +1204,17 @@ def device():
         d.xg_exchange_w.argtypes = [vp, ip, ip, ip, C.POINTER(Ext), i64, C.POINTER(i64), C.POINTER(ip), ip, vp, vp,
                                     C.POINTER(Timer), ip, ip, C.POINTER(RunOpts), C.POINTER(i64), C.POINTER(i64),
                                     C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
+        d.xg_exchange_wv.argtypes = [vp, ip, ip, ip, C.POINTER(Vec), i64, C.POINTER(i64), C.POINTER(ip), ip, vp, vp,
+                                     C.POINTER(Timer), ip, ip, C.POINTER(RunOpts), C.POINTER(i64), C.POINTER(i64),
+                                     C.POINTER(C.c_double), C.c_char_p, C.c_size_t]
+        d.xg_exchange_wv_tiles.restype = i64
+        d.xg_exchange_wv_tiles.argtypes = []
+        d.xg_vecplace_load.argtypes = [vp, vp, C.POINTER(VRow), i64, C.POINTER(vp)]
+        d.xg_vecplace_run.argtypes = [vp, C.POINTER(C.c_double)]
+        d.xg_vecplace_free.argtypes = [vp]
+        d.xg_vecplace_tiles.restype = i64
+        d.xg_vecplace_tiles.argtypes = [vp]
+        d.xg_vecplace_dispatches.argtypes = [vp]
         d.xg_plan_displs.argtypes = [vp, C.POINTER(i64), ip]
         d.xg_ktime_begin.argtypes = [vp, ip, ip]
         d.xg_ktime_end.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(ip), C.POINTER(i64)]
@@ -1492,6 +1585,104 @@ def place_check(run):
     src = chk_spans(run, [(sb, so, n) for (sb, so, _db, _do, n) in cp])
     dst = chk_spans(run, [(db, do, n) for (_sb, _so, db, do, n) in cp])
     return [run.ext_index[k] for k in range(len(cp)) if src[k] != dst[k]]
+
+
+def exchange_wv(ctx, method, procs, cb_nodes, vecs, dom_bytes, rank_list, comm_size, send, recv, it=0, ntimes=1,
+                verify=True, proc_node=1, pack_form=-1):
+    """xg_exchange_wv: exchange_w with the placement described by strided runs (Vec records or (rank,
+    agg, off, len, stride, count) tuples), placed by one copy_kernel_v launch.  Returns (rc, bad_slots,
+    bad_vecs, place_s, [Timer of every hosted rank], error text), as exchange_w does; vec_tiles() then
+    tells how many copy_kernel_v workgroups the placement ran (0: it went by the expansion)."""
+    d = device()
+    o = RunOpts()
+    d.xg_run_opts_default(C.byref(o))
+    o.verify, o.proc_node = 1 if verify else 0, proc_node
+    if pack_form >= 0:
+        o.pack_form = pack_form
+    lo, hi = C.c_int(), C.c_int()
+    host().xg_block_range(procs, ctx.nranks, ctx.rank, C.byref(lo), C.byref(hi))
+    timers = (Timer * max(1, hi.value - lo.value))()
+    rl = (C.c_int * cb_nodes)(*rank_list)
+    arr, n = _vec_array(vecs)
+    dom = (C.c_int64 * max(1, cb_nodes))(*[int(x) for x in dom_bytes])
+    bad, bad_v, place_s = C.c_int64(), C.c_int64(), C.c_double()
+    err = C.create_string_buffer(512)
+    rc = d.xg_exchange_wv(ctx.handle, method, procs, cb_nodes, arr, n, dom, rl, comm_size, C.c_void_p(send),
+                          C.c_void_p(recv), timers, it, ntimes, C.byref(o), C.byref(bad), C.byref(bad_v),
+                          C.byref(place_s), err, 512)
+    return rc, bad.value, bad_v.value, place_s.value, list(timers)[:hi.value - lo.value], err.value.decode()
+
+
+def vec_tiles():
+    """xg_exchange_wv_tiles: the copy_kernel_v workgroups of this process's last exchange_wv placement"""
+    return device().xg_exchange_wv_tiles()
+
+
+class VecPlace:
+    """One GPU's strided placement on its own: rows (VRow records or tuples; Schedule.vec_rows gives
+    a vec list's) loaded as one copy_kernel_v launch (xg_vecplace_load) over regions of region_bytes
+    whose SEND / RECV are the caller's (addresses as int) or allocated here.  XGError for rows the
+    host builder refuses: nothing has run then."""
+
+    def __init__(self, ctx, rows, region_bytes, send=None, recv=None, vec_index=None):
+        d = device()
+        self.ctx = ctx
+        self.rows = [r if isinstance(r, VRow) else VRow(*[int(x) for x in r]) for r in rows]
+        self.vec_index = list(vec_index) if vec_index is not None else list(range(len(self.rows)))
+        rb = list(region_bytes) + [0] * (NBUF - len(region_bytes))
+        self.regions = Regions.adopt(ctx, rb, send=send, recv=recv)
+        self._r = self.regions._r
+        self._v = C.c_void_p()
+        arr, n = _vrow_array(self.rows)
+        rc = d.xg_vecplace_load(ctx.handle, self._r, arr, n, C.byref(self._v))
+        if rc:
+            self.regions.close()
+            self.regions = None
+            raise XGError("xg_vecplace_load failed with code %d (see stderr)" % rc)
+
+    def run(self):
+        """one timed run -> the launch's device seconds"""
+        t = C.c_double()
+        _check(_dev.xg_vecplace_run(self._v, C.byref(t)), "xg_vecplace_run")
+        return t.value
+
+    @property
+    def tiles(self):
+        return _dev.xg_vecplace_tiles(self._v)
+
+    @property
+    def dispatches(self):
+        return _dev.xg_vecplace_dispatches(self._v)
+
+    def close(self):
+        if getattr(self, "_v", None):
+            _check(_dev.xg_vecplace_free(self._v), "xg_vecplace_free")
+            self._v = None
+        if getattr(self, "regions", None):
+            self.regions.close()
+            self.regions = None
+
+
+def vec_check(run, batch=65536):
+    """A VecPlace after its run: xg_chk_spans of every block of every row on both sides of the
+    placement, at most `batch` spans a launch.  Returns the list indices (vec_index) of the rows with
+    a differing block, ascending."""
+    bad, src, dst, who = set(), [], [], []
+
+    def flush():
+        a, b = chk_spans(run, src), chk_spans(run, dst)
+        bad.update(k for k, x, y in zip(who, a, b) if x != y)
+        del src[:], dst[:], who[:]
+    for k, r in enumerate(run.rows):
+        for j in range(r.count):
+            src.append((r.src_buf, r.src_off + j * r.src_step, r.len))
+            dst.append((r.dst_buf, r.dst_off + j * r.dst_step, r.len))
+            who.append(k)
+            if len(who) == batch:
+                flush()
+    if who:
+        flush()
+    return sorted(run.vec_index[k] for k in bad)
 
 
 class MethodRun:
