@@ -364,7 +364,7 @@ int xg_vecplace_free(xg_vecplace *v);
 int64_t xg_vecplace_tiles(const xg_vecplace *v);
 int xg_vecplace_dispatches(const xg_vecplace *v);
 
-/* xg_exchange_w with the placement described by STRIDED RUNS (exchange_wv.c; the list rules,
+/* xg_exchange_w with the placement described by STRIDED RUNS (exchange_w.c too; the list rules,
  * xg_vecs_check and xg_vecs_expand: xg_sched.h): what xg_exchange_w does for xg_vecs_expand of the
  * list, byte for byte, without ever building that expansion -- the list is judged by xg_vecs_check,
  * the pair lengths are xg_vecs_lens', the placement is one copy_kernel_v launch over the GPU's rows

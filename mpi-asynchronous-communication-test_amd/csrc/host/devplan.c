@@ -16,7 +16,7 @@
 /* Growable arrays of the device-plan builder.  The builder runs on every rank of a job and
  * must not stop one rank alone: when the host runs out of memory, a push lands in `sink` and
  * `fail` is set; xg_devplan_build_form then frees what it built and returns NULL, which the
- * caller turns into an error every rank agrees on (methods.c peers_agree). */
+ * caller turns into an error every rank agrees on (agree.h: agree_peers). */
 typedef struct { xg_copy *v; int n, cap, fail; xg_copy sink; } cvec;
 typedef struct { xg_p2p *v; int n, cap, fail; xg_p2p sink; } pvec;
 static xg_copy *cpush(cvec *c)

@@ -29,6 +29,7 @@
 #include <time.h>
 #include <unistd.h>
 
+#include "agree.h"
 #include "rdzv.h"
 #include "xg.h"
 #include "xg_sched.h"
@@ -222,27 +223,20 @@ int main(int argc, char **argv)
          * started with different ones would post calls nobody pairs and hang -- compare a
          * digest (FNV-1a of argv and the planning settings, in 16-bit parts) first */
         static const char *keys[] = {"XG_PROCS", "XG_VERIFY", "XG_SELF_MAX", NULL};
-        uint64_t h = 0xcbf29ce484222325ull;
-        double red[8];
-        int k;
+        uint64_t h = AGREE_FNV_INIT;
+        int k, differ = 0;
         for (k = 1; k <= argc; ++k) {
             const char *str = k < argc ? argv[k] : "";
-            size_t j, n = strlen(str) + 1;
-            for (j = 0; j < n; ++j) h = (h ^ (unsigned char)str[j]) * 0x100000001b3ull;
+            h = agree_fnv(h, str, strlen(str) + 1);
         }
         for (k = 0; keys[k]; ++k) {
             const char *v = getenv(keys[k]);
-            size_t j, n = v ? strlen(v) + 1 : 0;
-            for (j = 0; j < n; ++j) h = (h ^ (unsigned char)v[j]) * 0x100000001b3ull;
-            h = (h ^ (unsigned char)(k + 1)) * 0x100000001b3ull;
+            const unsigned char tag = (unsigned char)(k + 1);
+            if (v) h = agree_fnv(h, v, strlen(v) + 1);
+            h = agree_fnv(h, &tag, 1);
         }
-        for (k = 0; k < 4; ++k) {
-            red[k] = (double)((h >> (16 * k)) & 0xffff);
-            red[4 + k] = -red[k];
-        }
-        XGCALL(xg_allreduce_max(ctx, red, 8));
-        for (k = 0; k < 4; ++k)
-            if (red[k] != -red[4 + k]) DIE("the GPU processes were started with different arguments or settings");
+        XGCALL(agree_digest(ctx, h, &differ));
+        if (differ) DIE("the GPU processes were started with different arguments or settings");
     }
     if (rank == 0 && rdzv_path[0]) unlink(rdzv_path);
 

@@ -141,7 +141,7 @@ def test_processes_started_differently_refuse(exes, tmp_path, differ):
 def test_allocation_failure_on_one_rank_stops_every_rank(exes, tmp_path, G, self_max):
     """GPU 1's HBM regions cannot be allocated (XG_HOST_DEV_FAIL_ALLOC, as hipMalloc fails when
     HBM is exhausted): every rank learns it in one MAX reduction before the exchange's first call
-    (methods.c peers_agree) and every rank exits 1 naming the failure -- none waits for a peer that
+    (agree.h agree_peers) and every rank exits 1 naming the failure -- none waits for a peer that
     stopped, none posts a call nobody pairs.  With XG_SELF_MAX at 0 and 1 GiB (the pairing proof
     checks the lists posted with that value, xg_self_max)."""
     p = _run(exes["test"], ["-m", 1, "-a", 3, "-d", 3000, "--procs", 7, "--gpus", G], tmp_path, timeout=90,

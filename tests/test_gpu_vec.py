@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 
 S, R = 0, 1
 POISON = 0xA5
-VEC_LEN_MAX = 1024              # kVecLenMax (host/exchange_wv.c): the routing threshold
+VEC_LEN_MAX = 1024              # kVecLenMax (host/exchange_w.c): the routing threshold
 PHASE_LENS = list(range(1, 50)) + [63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 4095, 4096, 4097]
 
 
