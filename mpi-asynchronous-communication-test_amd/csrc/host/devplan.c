@@ -1,8 +1,10 @@
 /*
  * devplan.c -- the per-GPU device plan of a compiled schedule (xg_devplan_build_form): per step,
  * the GPU's local copies, packs into per-peer staging, its RCCL calls in the direct, packed
- * one-sided / two-sided or relay form, and unpacks.  Plain C99, no HIP.  See include/xg_sched.h;
- * the calls each step posts and their pairing proof are calls.c.
+ * one-sided / two-sided or relay form, and unpacks.  The builder holds its state in one context
+ * (bcx), indexes each step's messages by GPU pair once (step_index) and runs the step as named parts
+ * (step_*); a peer's sends and receives come from one body per form, given a direction.  Plain C99,
+ * no HIP.  See include/xg_sched.h; the calls each step posts and their pairing proof are calls.c.
  */
 #include "sched_int.h"
 
@@ -17,30 +19,19 @@
  * must not stop one rank alone: when the host runs out of memory, a push lands in `sink` and
  * `fail` is set; xg_devplan_build_form then frees what it built and returns NULL, which the
  * caller turns into an error every rank agrees on (agree.h: agree_peers). */
-typedef struct { xg_copy *v; int n, cap, fail; xg_copy sink; } cvec;
-typedef struct { xg_p2p *v; int n, cap, fail; xg_p2p sink; } pvec;
-static xg_copy *cpush(cvec *c)
+typedef struct { void *v; size_t esz; int n, cap, fail; union { xg_copy c; xg_p2p p; } sink; } gvec;
+static void *gpush(gvec *c)     /* -> a zeroed new element of esz bytes */
 {
     if (c->n == c->cap) {
         const int cap = c->cap ? 2 * c->cap : 256;
-        xg_copy *v = c->fail ? NULL : (xg_copy *)realloc(c->v, sizeof(xg_copy) * cap);
-        if (!v) { c->fail = 1; memset(&c->sink, 0, sizeof c->sink); return &c->sink; }
+        void *v = c->fail ? NULL : realloc(c->v, c->esz * cap);
+        if (!v) { c->fail = 1; return memset(&c->sink, 0, sizeof c->sink); }
         c->v = v; c->cap = cap;
     }
-    memset(&c->v[c->n], 0, sizeof(xg_copy));
-    return &c->v[c->n++];
+    return memset((char *)c->v + c->esz * c->n++, 0, c->esz);
 }
-static xg_p2p *ppush(pvec *c)
-{
-    if (c->n == c->cap) {
-        const int cap = c->cap ? 2 * c->cap : 256;
-        xg_p2p *v = c->fail ? NULL : (xg_p2p *)realloc(c->v, sizeof(xg_p2p) * cap);
-        if (!v) { c->fail = 1; memset(&c->sink, 0, sizeof c->sink); return &c->sink; }
-        c->v = v; c->cap = cap;
-    }
-    memset(&c->v[c->n], 0, sizeof(xg_p2p));
-    return &c->v[c->n++];
-}
+static xg_copy *cpush(gvec *c) { return (xg_copy *)gpush(c); }
+static xg_p2p *ppush(gvec *c) { return (xg_p2p *)gpush(c); }
 
 void xg_devplan_free(xg_devplan *p)
 {
@@ -60,11 +51,10 @@ static int use_pack(int n, int64_t total, int64_t pack_max_seg, int64_t pack_min
 typedef struct { int64_t *base[XG_NBUF]; } plan_bases;
 
 /* -> 0, or -1 when the host is out of memory (pb is then freeable) */
-static int plan_bases_init(plan_bases *pb, const xg_sched *s, int G, int g)
+static int plan_bases_init(plan_bases *pb, const xg_sched *s, int G)
 {
     int lo, hi, r, k, fail = 0;
     int64_t scr = 0;
-    (void)g;
     for (k = 0; k < XG_NBUF; ++k) fail |= !(pb->base[k] = (int64_t *)calloc(s->P + 1, sizeof(int64_t)));
     if (fail) return -1;
     for (r = 0; r < s->P; ++r) {
@@ -90,17 +80,11 @@ static int64_t dst_off(const plan_bases *pb, const xg_msg *m) { return pb->base[
 /* a message that moves device bytes (not a size message, not empty) */
 static int moves(const xg_msg *m) { return m->len > 0 && !(m->flags & XG_MSG_CTRL); }
 
-/* a rank-local memcpy through a TAM aggregation buffer */
+/* a rank-local memcpy through a TAM aggregation buffer.  It never crosses GPUs: XG_MSG_COPY is set
+ * on the self copies alone, which sched.c's do_match makes with src == dst (one rank, one GPU) */
 static int is_stage(const xg_msg *m)
 {
     return (m->flags & XG_MSG_COPY) && (m->sbuf == XG_BUF_SCRATCH || m->dbuf == XG_BUF_SCRATCH);
-}
-
-static void local_copy(xg_copy *c, const plan_bases *pb, const xg_msg *m)
-{
-    c->src_buf = m->sbuf; c->src_off = src_off(pb, m);
-    c->dst_buf = m->dbuf; c->dst_off = dst_off(pb, m);
-    c->len = m->len;
 }
 
 xg_devplan *xg_devplan_build(const xg_sched *s, int ngpus, int g, int64_t pack_max_seg)
@@ -194,38 +178,6 @@ static int64_t os_layout(const xg_sched *s, const plan_bases *pb, oneside *o, in
     return cost;
 }
 
-/* the one-sided form of the messages of step [b, e) from GPU gs to GPU gd */
-static void os_build(const xg_sched *s, const plan_bases *pb, const int *order, int b, int e, int G, int gs,
-                     int gd, oneside *o)
-{
-    int k;
-    int64_t cost_d, cost_s;
-    o->n = 0;
-    for (k = b; k < e; ++k) {
-        const xg_msg *m = &s->msgs[order[k]];
-        if (moves(m) && xg_gpu_of(s->P, G, m->src) == gs && xg_gpu_of(s->P, G, m->dst) == gd) o->n++;
-    }
-    o->idx = (int *)malloc(sizeof(int) * ((size_t)o->n + 1));
-    o->run_b = (int *)malloc(sizeof(int) * ((size_t)o->n + 2));
-    o->staged = (unsigned char *)malloc((size_t)o->n + 1);
-    if (!o->idx || !o->run_b || !o->staged) {
-        free(o->idx); free(o->run_b); free(o->staged);
-        o->idx = o->run_b = NULL;
-        o->staged = NULL;
-        o->n = o->nrun = 0;
-        o->fail = 1;
-        return;
-    }
-    o->n = 0;
-    for (k = b; k < e; ++k) {
-        const xg_msg *m = &s->msgs[order[k]];
-        if (moves(m) && xg_gpu_of(s->P, G, m->src) == gs && xg_gpu_of(s->P, G, m->dst) == gd) o->idx[o->n++] = order[k];
-    }
-    cost_s = os_layout(s, pb, o, 1);
-    cost_d = os_layout(s, pb, o, 0);
-    if (cost_s < cost_d) os_layout(s, pb, o, 1);
-}
-
 /* frees the arrays; keeps `fail` for the caller to see */
 static void os_free(oneside *o)
 {
@@ -233,6 +185,148 @@ static void os_free(oneside *o)
     free(o->idx); free(o->run_b); free(o->staged);
     memset(o, 0, sizeof *o);
     o->fail = fail;
+}
+
+/* the one-sided form of a step's n messages msgs[] from one GPU to another (a bucket of the index) */
+static void os_build(const xg_sched *s, const plan_bases *pb, const int *msgs, int n, oneside *o)
+{
+    int64_t cost_d, cost_s;
+    o->n = n;
+    o->idx = (int *)malloc(sizeof(int) * ((size_t)o->n + 1));
+    o->run_b = (int *)malloc(sizeof(int) * ((size_t)o->n + 2));
+    o->staged = (unsigned char *)malloc((size_t)o->n + 1);
+    if (!o->idx || !o->run_b || !o->staged) { os_free(o); o->fail = 1; return; }
+    memcpy(o->idx, msgs, sizeof(int) * (size_t)n);
+    cost_s = os_layout(s, pb, o, 1);
+    cost_d = os_layout(s, pb, o, 0);
+    if (cost_s < cost_d) os_layout(s, pb, o, 1);
+}
+
+/* ---- the builder's context: all xg_devplan_build_form holds while it builds one GPU's plan.
+ * bcx_init allocates it and bcx_free frees it; a failed allocation sets `oom`, and the builder then
+ * frees what it has and returns NULL (nothing exits on out-of-memory: see gvec above). */
+enum { OUT = 0, IN = 1 };           /* a direction of this GPU's traffic with a peer p: [dir * G + p] */
+typedef struct {
+    const xg_sched *s;
+    xg_devplan *dp;                 /* the plan being built */
+    plan_bases pb;
+    int G, g, form, oom;
+    int64_t pack_max_seg, pack_min;
+    int *cnt, *order;               /* messages sorted by step: step st is order[cnt[st] .. cnt[st + 1]) */
+    gvec pre, post, pp;             /* copies before the exchange, copies after it, RCCL calls */
+    int32_t *posts;                 /* xgi_step_posts_of's answer */
+    /* of the step being built: */
+    int64_t sbase, rbase, soff;     /* STAGE_SEND / STAGE_RECV fill; STAGE_SEND bytes the send calls took */
+    int *bk, *bk_off;               /* the index (step_index) */
+    int64_t *vol_b;                 /* per direction and peer: bytes (0: no message; p = g: 0) */
+    oneside *os;                    /* per direction and peer: the one-sided layout of a packed list */
+    int64_t *rl_ei, *rl_p;          /* relay_step's egress [g] and ingress [G + g] bytes; pair bytes */
+    int *rl_w;                      /* a weighted step's shares (weighted_step) */
+    /* of the coalesced relay (rc_step): */
+    int dry;                        /* only sum the unpacked bytes (the relay area starts behind them) */
+    const int *w;                   /* weighted step: [(a * G + b) * G + h] = pair (a, b)'s share via h in
+                                       1/XG_WEIGHT_ONE (weighted_step); NULL: relay_cut's uniform pieces */
+    const xg_msg **pm; int64_t *po, *pl;    /* pieces of the call being built: message, offset in it, length */
+    int64_t *blk;                   /* [a * G + b]: where the block of a's pieces for b that g relays lies */
+    int64_t ubase, rlbase, rl;      /* STAGE_RECV: unpack fill, relay area start / fill */
+} bcx;
+
+static void *bcx_alloc(bcx *x, size_t n, size_t size)
+{
+    void *p = calloc(n, size);
+    x->oom |= !p;
+    return p;
+}
+
+static void bcx_init(bcx *x, const xg_sched *s, int G, int g, int64_t pack_max_seg, int64_t pack_min, int form)
+{
+    const size_t nst = (size_t)s->nsteps, GG = (size_t)G * G;
+    size_t widest = 0;
+    int i;
+    memset(x, 0, sizeof *x);
+    if (form != XG_PACK_TWO_SIDED && form != XG_PACK_ONE_SIDED && form != XG_RELAY && form != XG_RELAY_COALESCED)
+        form = XG_PACK_FORM_DEFAULT;
+    x->s = s; x->G = G; x->g = g; x->form = form; x->pack_min = pack_min;
+    x->pack_max_seg = form == XG_RELAY || form == XG_RELAY_COALESCED ? 0 : pack_max_seg;   /* every other step is direct */
+    x->pre.esz = x->post.esz = sizeof(xg_copy); x->pp.esz = sizeof(xg_p2p);
+    x->oom |= plan_bases_init(&x->pb, s, G) != 0;
+    x->cnt = (int *)bcx_alloc(x, nst + 2, sizeof(int));
+    x->order = (int *)bcx_alloc(x, (size_t)s->nmsg + 1, sizeof(int));
+    if (x->oom) return;
+    /* counting sort of messages by step, stable in message order (a step's count two places up, so
+     * that filling `order` leaves every cnt[st] at its step's begin) */
+    for (i = 0; i < s->nmsg; ++i) x->cnt[s->msgs[i].step + 2]++;
+    for (i = 0; i < s->nsteps; ++i) {
+        if ((size_t)x->cnt[i + 2] > widest) widest = (size_t)x->cnt[i + 2];
+        x->cnt[i + 2] += x->cnt[i + 1];
+    }
+    for (i = 0; i < s->nmsg; ++i) x->order[x->cnt[s->msgs[i].step + 1]++] = i;
+    x->posts = (int32_t *)bcx_alloc(x, nst + 1, sizeof(int32_t));
+    x->bk = (int *)bcx_alloc(x, widest + 1, sizeof(int));
+    x->bk_off = (int *)bcx_alloc(x, GG + 2, sizeof(int));
+    x->vol_b = (int64_t *)bcx_alloc(x, 2 * (size_t)G, sizeof(int64_t));
+    x->os = (oneside *)bcx_alloc(x, 2 * (size_t)G, sizeof(oneside));
+    x->rl_ei = (int64_t *)bcx_alloc(x, 2 * (size_t)G, sizeof(int64_t));
+    x->rl_p = (int64_t *)bcx_alloc(x, GG, sizeof(int64_t));
+    x->rl_w = (int *)bcx_alloc(x, GG * G, sizeof(int));
+    x->pm = (const xg_msg **)bcx_alloc(x, widest + 1, sizeof(xg_msg *));
+    x->po = (int64_t *)bcx_alloc(x, widest + 1, sizeof(int64_t));
+    x->pl = (int64_t *)bcx_alloc(x, widest + 1, sizeof(int64_t));
+    x->blk = (int64_t *)bcx_alloc(x, GG, sizeof(int64_t));
+    x->dp = (xg_devplan *)bcx_alloc(x, 1, sizeof(xg_devplan));
+    if (x->dp) x->dp->steps = (xg_stepplan *)bcx_alloc(x, nst + 1, sizeof(xg_stepplan));
+}
+
+/* frees all but the plan itself */
+static void bcx_free(bcx *x)
+{
+    free(x->pre.v); free(x->post.v); free(x->pp.v); free(x->cnt); free(x->order); free(x->posts);
+    free(x->bk); free(x->bk_off); free(x->vol_b); free(x->os); free(x->rl_ei); free(x->rl_p); free(x->rl_w);
+    free((void *)x->pm); free(x->po); free(x->pl); free(x->blk);
+    plan_bases_free(&x->pb);
+}
+
+static const xg_msg *step_msg(const bcx *x, int k) { return &x->s->msgs[x->order[k]]; }
+
+static void local_copy(bcx *x, const xg_msg *m)
+{
+    xg_copy *c = cpush(&x->pre);
+    c->src_buf = m->sbuf; c->src_off = src_off(&x->pb, m);
+    c->dst_buf = m->dbuf; c->dst_off = dst_off(&x->pb, m);
+    c->len = m->len; x->dp->local_bytes += m->len;
+}
+
+/* The filter, stated once: a moving, non-stage message belongs to the bucket of its (source GPU,
+ * destination GPU), source GPU * G + destination GPU; any other message to none (-1). */
+static int msg_bucket(const bcx *x, const xg_msg *m)
+{
+    if (!moves(m) || is_stage(m)) return -1;
+    return xg_gpu_of(x->s->P, x->G, m->src) * x->G + xg_gpu_of(x->s->P, x->G, m->dst);
+}
+
+/* The index of step [b, e): bucket (a, b') = bk[bk_off[a * G + b'] .. bk_off[a * G + b' + 1]), in
+ * message order.  Every walk of "the step's messages from GPU a to GPU b'" goes over a bucket;
+ * (g, g) is GPU g's local copies.  (relay_step and relay_calls walk the step in message order
+ * across pairs: the relay area is laid out in that order.) */
+static void step_index(bcx *x, int b, int e)
+{
+    int k, c;
+    memset(x->bk_off, 0, sizeof(int) * ((size_t)x->G * x->G + 2));
+    for (k = b; k < e; ++k)
+        if ((c = msg_bucket(x, step_msg(x, k))) >= 0) x->bk_off[c + 2]++;
+    for (c = 0; c < x->G * x->G; ++c) x->bk_off[c + 2] += x->bk_off[c + 1];
+    for (k = b; k < e; ++k)         /* filling leaves every bk_off[c] at its bucket's begin */
+        if ((c = msg_bucket(x, step_msg(x, k))) >= 0) x->bk[x->bk_off[c + 1]++] = x->order[k];
+}
+
+static const xg_msg *bk_msg(const bcx *x, int k) { return &x->s->msgs[x->bk[k]]; }
+
+/* the bucket this GPU shares with peer p in direction dir (p = g: its local copies) -> bk[lo .. *hi) */
+static int peer_bucket(const bcx *x, int p, int dir, int *hi)
+{
+    const int c = dir == OUT ? x->g * x->G + p : p * x->G + x->g;
+    *hi = x->bk_off[c + 1];
+    return x->bk_off[c];
 }
 
 /* ---- relay form (XG_RELAY, xg_sched.h): two-phase (Valiant) routing of one step.  Every
@@ -244,27 +338,28 @@ static void os_free(oneside *o)
  * cost and every cross-GPU message is >= XG_RELAY_MIN_BYTES (smaller pieces are latency, not
  * bandwidth).  Pairwise m9 / m10 (mpi_test.c:510-597, :421-508; partner rank ^ i, :531-545) at
  * configs[3] put every GPU's 16 MiB round on ONE of its 7 links: 16 -> 4 MiB of link time per
- * round.  Every GPU decides from the same message list, so all agree. */
-static int relay_step(const xg_sched *s, const int *order, int b, int e, int G, int64_t *egress, int64_t *ingress,
-                      int64_t *pair)
+ * round.  Every GPU decides from the same message list, so all agree.  -> 1: relay it; 0: the uniform
+ * cut does not pay (rl_p holds the step's GPU-pair bytes); -1: no routing can (nothing to relay) */
+static int relay_step(const bcx *x, int b, int e)
 {
+    const int G = x->G;
+    int64_t *const egress = x->rl_ei, *const ingress = x->rl_ei + G, *const pair = x->rl_p;
     int k, g, any = 0;
     int64_t direct = 0, emax = 0, imax = 0;
-    if (G < 3) return 0;
-    memset(egress, 0, sizeof(int64_t) * (size_t)G);
-    memset(ingress, 0, sizeof(int64_t) * (size_t)G);
+    if (G < 3) return -1;
+    memset(egress, 0, sizeof(int64_t) * 2 * (size_t)G);     /* and ingress */
     memset(pair, 0, sizeof(int64_t) * (size_t)G * G);
     for (k = b; k < e; ++k) {
-        const xg_msg *m = &s->msgs[order[k]];
-        const int gs = xg_gpu_of(s->P, G, m->src), gd = xg_gpu_of(s->P, G, m->dst);
-        if (!moves(m) || is_stage(m) || gs == gd) continue;
-        if (m->len < XG_RELAY_MIN_BYTES) return 0;
+        const xg_msg *m = step_msg(x, k);
+        const int c = msg_bucket(x, m), gs = c / G, gd = c % G;
+        if (c < 0 || gs == gd) continue;
+        if (m->len < XG_RELAY_MIN_BYTES) return -1;
         egress[gs] += m->len;
         ingress[gd] += m->len;
         pair[(size_t)gs * G + gd] += m->len;
         any = 1;
     }
-    if (!any) return 0;
+    if (!any) return -1;
     for (g = 0; g < G * G; ++g) direct = pair[g] > direct ? pair[g] : direct;
     for (g = 0; g < G; ++g) {
         emax = egress[g] > emax ? egress[g] : emax;
@@ -286,7 +381,7 @@ static int relay_gpu(int i, int gs, int gd)
     return h;
 }
 
-static void relay_push(pvec *pp, int peer, int is_send, int buf, int64_t off, int64_t len, int group)
+static void relay_push(gvec *pp, int peer, int is_send, int buf, int64_t off, int64_t len, int group)
 {
     xg_p2p *o;
     if (len <= 0) return;            /* a 0-byte piece (len < 16 G): no call on either side */
@@ -297,22 +392,24 @@ static void relay_push(pvec *pp, int peer, int is_send, int buf, int64_t off, in
 /* GPU g's calls of one relayed step: group 0 = pieces 0 straight to the destination and pieces
  * 2 + i to relay R[i] (into its STAGE_RECV at *rbase on); group 1 = pieces 1 straight, and what g
  * holds as a relay forwarded to the destination.  Every list is in message order, so the k-th
- * send of any GPU to any other pairs with the k-th receive there, group by group. */
-static void relay_calls(const xg_sched *s, const plan_bases *pb, const int *order, int b, int e, int G, int g,
-                        pvec *pp, int64_t *rbase)
+ * send of any GPU to any other pairs with the k-th receive there, group by group -- and the relay
+ * area is laid out in that order across GPU pairs: this walk is over the step, not over buckets. */
+static void relay_calls(bcx *x, int b, int e)
 {
+    const int G = x->G, g = x->g;
+    gvec *const pp = &x->pp;
     int grp, k, i;
-    int64_t roff = *rbase;
+    int64_t roff = x->rbase;
     for (grp = 0; grp < 2; ++grp) {
-        roff = *rbase;
+        roff = x->rbase;
         for (k = b; k < e; ++k) {
-            const xg_msg *m = &s->msgs[order[k]];
-            const int gs = xg_gpu_of(s->P, G, m->src), gd = xg_gpu_of(s->P, G, m->dst);
+            const xg_msg *m = step_msg(x, k);
+            const int c = msg_bucket(x, m), gs = c / G, gd = c % G;
             const int ri = g != gs && g != gd ? g - (g > gs) - (g > gd) : -1;   /* g's relay index */
             int64_t so, dof;
-            if (!moves(m) || is_stage(m) || gs == gd) continue;
-            so = src_off(pb, m);
-            dof = dst_off(pb, m);
+            if (c < 0 || gs == gd) continue;
+            so = src_off(&x->pb, m);
+            dof = dst_off(&x->pb, m);
             if (g == gs) {
                 relay_push(pp, gd, 1, m->sbuf, so + relay_cut(m->len, grp, G),
                            relay_cut(m->len, grp + 1, G) - relay_cut(m->len, grp, G), grp);
@@ -335,7 +432,7 @@ static void relay_calls(const xg_sched *s, const plan_bases *pb, const int *orde
             }
         }
     }
-    *rbase = roff;
+    x->rbase = roff;
 }
 
 /* ---- coalesced relay form (XG_RELAY_COALESCED, xg_sched.h): relay_step's steps, relay_cut's
@@ -358,21 +455,6 @@ static void relay_calls(const xg_sched *s, const plan_bases *pb, const int *orde
  * blocks behind them.  A pairwise round: G - 1 sends + G - 1 receives per group. */
 #define XG_WEIGHT_ONE 1024      /* a weighted step's shares: 1/1024ths of each GPU pair's bytes */
 
-typedef struct {
-    const xg_sched *s;
-    const plan_bases *pb;
-    int G, g, dry;          /* dry: only sum the unpacked bytes (the relay area starts behind them) */
-    const int *bk, *bk_off; /* the step's cross messages by (source GPU, destination GPU), message order */
-    const int *w;           /* weighted step: [(a * G + b) * G + h] = pair (a, b)'s share via h in
-                               1/XG_WEIGHT_ONE (weighted_step); NULL: relay_cut's uniform pieces */
-    const xg_msg **pm;      /* pieces of the call being built: message, offset in it, length */
-    int64_t *po, *pl;
-    int64_t *blk;           /* [a * G + b]: where the block of a's pieces for b that g relays lies */
-    cvec *pre, *post;
-    pvec *pp;
-    int64_t sbase, ubase, rlbase, rl;   /* STAGE_SEND fill; STAGE_RECV unpack fill, relay area start / fill */
-} rcx;
-
 /* the piece of a message gs -> gd that travels via GPU h (relay_calls' assignment) */
 static int rc_piece(int gs, int gd, int h) { return h == gd ? 0 : h == gs ? 1 : 2 + h - (h > gs) - (h > gd); }
 
@@ -381,7 +463,7 @@ static int64_t wcut(int64_t len, int c) { return c >= XG_WEIGHT_ONE ? len : ((le
 
 /* [lo, hi) of message m (a -> b) that travels via h: relay_cut's piece, or a weighted step's share,
  * the shares laid out in hop order (h = 0 .. G-1) */
-static void rc_range(const rcx *x, const xg_msg *m, int a, int b, int h, int64_t *lo, int64_t *hi)
+static void rc_range(const bcx *x, const xg_msg *m, int a, int b, int h, int64_t *lo, int64_t *hi)
 {
     if (x->w) {
         const int *w = &x->w[((size_t)a * x->G + b) * x->G];
@@ -398,7 +480,7 @@ static void rc_range(const rcx *x, const xg_msg *m, int a, int b, int h, int64_t
 
 /* the pieces of the messages a -> b that travel via h (b < 0: every b other than a and h,
  * ascending), each message's in message order -> how many */
-static int rc_collect(rcx *x, int a, int b, int h)
+static int rc_collect(bcx *x, int a, int b, int h)
 {
     const int G = x->G, b0 = b < 0 ? 0 : b, b1 = b < 0 ? G : b + 1;
     int n = 0, bb, k;
@@ -415,7 +497,7 @@ static int rc_collect(rcx *x, int a, int b, int h)
     return n;
 }
 
-static int64_t rc_total(const rcx *x, int n)
+static int64_t rc_total(const bcx *x, int n)
 {
     int64_t t = 0;
     int i;
@@ -428,56 +510,56 @@ static int64_t rc_total(const rcx *x, int n)
  * at ~5 TB/s each way: >= 3 us) -- configs[4]'s 64 MiB segments, whose pieces are 8 MiB.  Both ends
  * of a call apply it to the same piece list, so the calls still pair one to one. */
 #define XG_COALESCE_SPLIT ((int64_t)4 << 20)
-static int rc_split(const rcx *x, int n) { return n > 1 && rc_total(x, n) >= XG_COALESCE_SPLIT * n; }
+static int rc_split(const bcx *x, int n) { return n > 1 && rc_total(x, n) >= XG_COALESCE_SPLIT * n; }
 
 /* send the n collected pieces to peer in group grp: in place, or packed into STAGE_SEND */
-static void rc_send(rcx *x, int n, int peer, int grp)
+static void rc_send(bcx *x, int n, int peer, int grp)
 {
     int64_t t = 0;
     int i;
     if (!n || x->dry) return;
     if (n == 1 || rc_split(x, n)) {
         for (i = 0; i < n; ++i)
-            relay_push(x->pp, peer, 1, x->pm[i]->sbuf, src_off(x->pb, x->pm[i]) + x->po[i], x->pl[i], grp);
+            relay_push(&x->pp, peer, 1, x->pm[i]->sbuf, src_off(&x->pb, x->pm[i]) + x->po[i], x->pl[i], grp);
         return;
     }
     for (i = 0; i < n; ++i) {
-        xg_copy *c = cpush(x->pre);
-        c->src_buf = x->pm[i]->sbuf; c->src_off = src_off(x->pb, x->pm[i]) + x->po[i];
+        xg_copy *c = cpush(&x->pre);
+        c->src_buf = x->pm[i]->sbuf; c->src_off = src_off(&x->pb, x->pm[i]) + x->po[i];
         c->dst_buf = XG_BUF_STAGE_SEND; c->dst_off = x->sbase + t;
         c->len = x->pl[i];
         t += x->pl[i];
     }
-    relay_push(x->pp, peer, 1, XG_BUF_STAGE_SEND, x->sbase, t, grp);
+    relay_push(&x->pp, peer, 1, XG_BUF_STAGE_SEND, x->sbase, t, grp);
     x->sbase += t;
 }
 
 /* receive the n collected pieces (all ending at this GPU) from peer: in place, or into the unpack
  * area of STAGE_RECV with one unpack copy per piece */
-static void rc_recv(rcx *x, int n, int peer, int grp)
+static void rc_recv(bcx *x, int n, int peer, int grp)
 {
     int64_t t = 0;
     int i;
     if (!n) return;
     if (n == 1 || rc_split(x, n)) {
         for (i = 0; i < n && !x->dry; ++i)
-            relay_push(x->pp, peer, 0, x->pm[i]->dbuf, dst_off(x->pb, x->pm[i]) + x->po[i], x->pl[i], grp);
+            relay_push(&x->pp, peer, 0, x->pm[i]->dbuf, dst_off(&x->pb, x->pm[i]) + x->po[i], x->pl[i], grp);
         return;
     }
     for (i = 0; i < n && !x->dry; ++i) {
-        xg_copy *c = cpush(x->post);
+        xg_copy *c = cpush(&x->post);
         c->src_buf = XG_BUF_STAGE_RECV; c->src_off = x->ubase + t;
-        c->dst_buf = x->pm[i]->dbuf; c->dst_off = dst_off(x->pb, x->pm[i]) + x->po[i];
+        c->dst_buf = x->pm[i]->dbuf; c->dst_off = dst_off(&x->pb, x->pm[i]) + x->po[i];
         c->len = x->pl[i];
         t += x->pl[i];
     }
     if (x->dry) t = rc_total(x, n);
-    else relay_push(x->pp, peer, 0, XG_BUF_STAGE_RECV, x->ubase, t, grp);
+    else relay_push(&x->pp, peer, 0, XG_BUF_STAGE_RECV, x->ubase, t, grp);
     x->ubase += t;
 }
 
 /* GPU g's calls of one relayed step (dry: only the unpack area's size, x->ubase) */
-static void rc_step(rcx *x)
+static void rc_step(bcx *x)
 {
     const int G = x->G, g = x->g;
     int p, a, b, n;
@@ -492,11 +574,11 @@ static void rc_step(rcx *x)
             int64_t t = 0;
             if (rc_split(x, n))         /* (or one per piece, as the sender splits them) */
                 for (b = 0; b < n; ++b) {
-                    relay_push(x->pp, p, 0, XG_BUF_STAGE_RECV, at + t, x->pl[b], 0);
+                    relay_push(&x->pp, p, 0, XG_BUF_STAGE_RECV, at + t, x->pl[b], 0);
                     t += x->pl[b];
                 }
             else
-                relay_push(x->pp, p, 0, XG_BUF_STAGE_RECV, at, rc_total(x, n), 0);
+                relay_push(&x->pp, p, 0, XG_BUF_STAGE_RECV, at, rc_total(x, n), 0);
             for (t = 0, b = 0; b < G; ++b) {
                 if (b == p || b == g) continue;
                 x->blk[p * G + b] = at + t;
@@ -513,9 +595,9 @@ static void rc_step(rcx *x)
                 /* the block of a's pieces for p, as it lies (one call, or one per piece) */
                 int64_t at = x->blk[a * G + p];
                 if (rc_split(x, n))
-                    for (b = 0; b < n; at += x->pl[b], ++b) relay_push(x->pp, p, 1, XG_BUF_STAGE_RECV, at, x->pl[b], 1);
+                    for (b = 0; b < n; at += x->pl[b], ++b) relay_push(&x->pp, p, 1, XG_BUF_STAGE_RECV, at, x->pl[b], 1);
                 else
-                    relay_push(x->pp, p, 1, XG_BUF_STAGE_RECV, at, rc_total(x, n), 1);
+                    relay_push(&x->pp, p, 1, XG_BUF_STAGE_RECV, at, rc_total(x, n), 1);
             }
         rc_recv(x, rc_collect(x, p, g, p), p, 1);
         for (a = 0; a < G; ++a)
@@ -605,9 +687,9 @@ static void fw_memo_put(const double *D, int G, uint64_t key, const int *w, int 
     memcpy(m->w, w, sizeof(int) * (size_t)G * G * G);
 }
 
-/* The weighted split of step [b, e) into w[(a * G + b) * G + h] (1/XG_WEIGHT_ONE) -> 1 when the
- * step is to be weighted, 0 when it stays direct, -1 out of host memory */
-static int weighted_step(const xg_sched *s, const int *order, int b, int e, int G, int *w)
+/* The weighted split of a step of pair[a * G + b] bytes (relay_step's, where it returns 0) into
+ * w[(a * G + b) * G + h] (1/XG_WEIGHT_ONE) -> 1: weight the step, 0: it stays direct, -1: out of host memory */
+static int weighted_step(const int64_t *pair, int G, int *w)
 {
     uint64_t key = 0;
     const fw_memo *hit;
@@ -620,14 +702,7 @@ static int weighted_step(const xg_sched *s, const int *order, int b, int e, int 
     double *g0 = (double *)malloc(sizeof(double) * (size_t)G * G), *g1 = (double *)malloc(sizeof(double) * (size_t)G * G);
     if (!D || !pr || !y || !yb || !l0 || !l1 || !g0 || !g1) goto done;
     rc = 0;
-    if (G < 3) goto done;
-    for (k = b; k < e; ++k) {
-        const xg_msg *m = &s->msgs[order[k]];
-        const int gs = xg_gpu_of(s->P, G, m->src), gd = xg_gpu_of(s->P, G, m->dst);
-        if (!moves(m) || is_stage(m) || gs == gd) continue;
-        if (m->len < XG_RELAY_MIN_BYTES) goto done;
-        D[gs * G + gd] += (double)m->len;
-    }
+    for (i = 0; i < G * G; ++i) D[i] = (double)pair[i];     /* exact: sums of lengths, far below 2^53 */
     for (i = 0; i < G * G; ++i) {
         direct = D[i] > direct ? D[i] : direct;
         if (D[i] > 0) {
@@ -701,323 +776,244 @@ done:
     return rc;
 }
 
-/* the coalesced relay calls of step [b, e) for GPU g: packs into pre, calls into pp, unpacks into
- * post; *sbase / *rbase: the step's STAGE_SEND / STAGE_RECV bytes.  -> 0, or -1 out of host memory */
-static int relay_coalesced_calls(const xg_sched *s, const plan_bases *pb, const int *order, int b, int e, int G,
-                                 int g, const int *w, cvec *pre, pvec *pp, cvec *post, int64_t *sbase, int64_t *rbase)
+/* the coalesced relay calls of the step (w: a weighted step's shares, or NULL): packs into pre, calls
+ * into pp, unpacks into post, and the step's STAGE_SEND / STAGE_RECV bytes */
+static void relay_coalesced_calls(bcx *x, const int *w)
 {
-    int k, rc = -1;
-    int *bk_off = (int *)calloc((size_t)G * G + 1, sizeof(int)), *fill = (int *)calloc((size_t)G * G, sizeof(int));
-    int *bk = (int *)malloc(sizeof(int) * ((size_t)(e - b) + 1));
-    const xg_msg **pm = (const xg_msg **)malloc(sizeof(xg_msg *) * ((size_t)(e - b) + 1));
-    int64_t *po = (int64_t *)malloc(sizeof(int64_t) * ((size_t)(e - b) + 1));
-    int64_t *pl = (int64_t *)malloc(sizeof(int64_t) * ((size_t)(e - b) + 1));
-    int64_t *blk = (int64_t *)calloc((size_t)G * G, sizeof(int64_t));
-    rcx x;
-    if (!bk_off || !fill || !bk || !pm || !po || !pl || !blk) goto done;
+    x->w = w; x->ubase = x->rl = 0; x->dry = 1;
+    rc_step(x);                         /* the unpack area's size: the relay area goes behind it */
+    x->rlbase = x->ubase; x->ubase = 0; x->dry = 0;
+    rc_step(x);
+    x->rbase = x->rlbase + x->rl;
+}
+
+/* ---- the parts of one step, in the order xg_devplan_build_form runs them.  What deals with a peer
+ * takes a direction: OUT is the source end of bucket (g, p), STAGE_SEND and the pre copies, IN the
+ * destination end of bucket (p, g), STAGE_RECV and the post copies -- a GPU's sends and its peer's
+ * receives come from one body. */
+
+/* rank-local memcpy's through SCRATCH first, in a launch of their own: the local copies and packs
+ * of the step may read what they write in it */
+static void step_stage_copies(bcx *x, int b, int e)
+{
+    int k;
     for (k = b; k < e; ++k) {
-        const xg_msg *m = &s->msgs[order[k]];
-        const int gs = xg_gpu_of(s->P, G, m->src), gd = xg_gpu_of(s->P, G, m->dst);
-        if (moves(m) && !is_stage(m) && gs != gd) bk_off[gs * G + gd + 1]++;
+        const xg_msg *m = step_msg(x, k);
+        if (moves(m) && is_stage(m) && xg_gpu_of(x->s->P, x->G, m->src) == x->g) local_copy(x, m);
     }
-    for (k = 0; k < G * G; ++k) bk_off[k + 1] += bk_off[k];
-    for (k = b; k < e; ++k) {
-        const xg_msg *m = &s->msgs[order[k]];
-        const int gs = xg_gpu_of(s->P, G, m->src), gd = xg_gpu_of(s->P, G, m->dst);
-        if (moves(m) && !is_stage(m) && gs != gd) bk[bk_off[gs * G + gd] + fill[gs * G + gd]++] = order[k];
+}
+
+/* this GPU's local copies, and per direction and peer the bytes the pack decision goes by */
+static void step_local_copies(bcx *x)
+{
+    int i, k, hi;
+    for (k = peer_bucket(x, x->g, OUT, &hi); k < hi; ++k) local_copy(x, bk_msg(x, k));
+    for (i = 0; i < 2 * x->G; ++i) {        /* i = dir * G + p */
+        x->vol_b[i] = 0;
+        for (k = peer_bucket(x, i % x->G, i / x->G, &hi); k < hi && i % x->G != x->g; ++k)
+            x->vol_b[i] += bk_msg(x, k)->len;
     }
-    memset(&x, 0, sizeof x);
-    x.s = s; x.pb = pb; x.G = G; x.g = g; x.bk = bk; x.bk_off = bk_off; x.pm = pm; x.po = po; x.pl = pl;
-    x.blk = blk; x.pre = pre; x.post = post; x.pp = pp; x.w = w;
-    x.dry = 1;
-    rc_step(&x);                        /* the unpack area's size: the relay area goes behind it */
-    x.rlbase = x.ubase;
-    x.ubase = 0;
-    x.dry = 0;
-    rc_step(&x);
-    *sbase = x.sbase;
-    *rbase = x.rlbase + x.rl;
-    rc = 0;
-done:
-    free(bk_off); free(fill); free(bk); free(pm); free(po); free(pl); free(blk);
-    return rc;
+}
+
+/* the relay decision, the same on every GPU: 0 = the step's messages go as they are, 1 = relayed in
+ * relay_cut's uniform pieces, 2 = relayed in the weighted shares rl_w */
+static int step_relay(bcx *x, int b, int e)
+{
+    int r;
+    if (x->form != XG_RELAY && x->form != XG_RELAY_COALESCED) return 0;
+    r = relay_step(x, b, e);
+    if (r || x->form != XG_RELAY_COALESCED) return r > 0;
+    /* a step the uniform cut does not help may still take a weighted two-hop split */
+    r = weighted_step(x->rl_p, x->G, x->rl_w);
+    x->oom |= r < 0;
+    return r > 0 ? 2 : 0;
+}
+
+/* is the list exchanged with peer p in direction dir packed?  (both ends see the same list) */
+static int packed(const bcx *x, int p, int dir)
+{
+    int hi, lo = peer_bucket(x, p, dir, &hi);
+    return x->vol_b[dir * x->G + p] && use_pack(hi - lo, x->vol_b[dir * x->G + p], x->pack_max_seg, x->pack_min);
+}
+
+/* this GPU's end of message m: the source (OUT) or the destination (IN) */
+static void msg_end(const bcx *x, const xg_msg *m, int dir, int32_t *buf, int64_t *off)
+{
+    *buf = dir == OUT ? m->sbuf : m->dbuf;
+    *off = dir == OUT ? src_off(&x->pb, m) : dst_off(&x->pb, m);
+}
+
+/* the copy of message m between this GPU's end of it and staging at `at`: a pack into STAGE_SEND in
+ * the pre launch (OUT), an unpack out of STAGE_RECV in the post launch (IN) */
+static void stage_copy(bcx *x, int dir, const xg_msg *m, int64_t at)
+{
+    xg_copy *c = cpush(dir == OUT ? &x->pre : &x->post);
+    if (dir == OUT) {
+        msg_end(x, m, OUT, &c->src_buf, &c->src_off);
+        c->dst_buf = XG_BUF_STAGE_SEND; c->dst_off = at;
+    } else {
+        c->src_buf = XG_BUF_STAGE_RECV; c->src_off = at;
+        msg_end(x, m, IN, &c->dst_buf, &c->dst_off);
+    }
+    c->len = m->len;
+}
+
+/* is run r of a one-sided layout staged at this end?  The sender stages the runs of a
+ * destination-ordered layout, the receiver those of a source-ordered one; the rest move as they lie */
+static int os_staged(const oneside *o, int r, int dir) { return o->staged[r] && o->by_src == (dir == IN); }
+
+/* the staged copies of the packed list of peer p, back to back from `at` on: every message of the
+ * bucket (two-sided), or of the runs staged at this end (one-sided) -> their bytes */
+static int64_t staged_copies(bcx *x, int p, int dir, int64_t at)
+{
+    const oneside *o = &x->os[dir * x->G + p];
+    int64_t off = 0;
+    int r, k, hi;
+    if (x->form != XG_PACK_ONE_SIDED)
+        for (k = peer_bucket(x, p, dir, &hi); k < hi; ++k) {
+            stage_copy(x, dir, bk_msg(x, k), at + off);
+            off += bk_msg(x, k)->len;
+        }
+    else
+        for (r = 0; r < o->nrun; ++r)
+            for (k = o->run_b[r]; k < o->run_b[r + 1] && os_staged(o, r, dir); ++k) {
+                stage_copy(x, dir, os_msg(x->s, o, k), at + off);
+                off += os_msg(x->s, o, k)->len;
+            }
+    return off;
+}
+
+/* packs (into staging) join the pre-exchange copy launch, those of all peers ahead of any call; a
+ * coalesced relay's come with its calls and unpacks */
+static void step_packs(bcx *x, int relayed)
+{
+    int p, dir, lo, hi;
+    if (relayed && x->form == XG_RELAY_COALESCED) relay_coalesced_calls(x, relayed == 2 ? x->rl_w : NULL);
+    for (p = 0; p < x->G; ++p) {
+        /* the one-sided layout of every packed list of this GPU's, both directions */
+        for (dir = OUT; dir <= IN && x->form == XG_PACK_ONE_SIDED; ++dir) {
+            oneside *o = &x->os[dir * x->G + p];
+            lo = peer_bucket(x, p, dir, &hi);
+            if (packed(x, p, dir)) os_build(x->s, &x->pb, &x->bk[lo], hi - lo, o);
+            x->oom |= o->fail;
+        }
+        if (packed(x, p, OUT)) x->sbase += staged_copies(x, p, OUT, x->sbase);
+    }
+}
+
+/* one call of len bytes: at message m's end on this GPU, or (m NULL) at the staging region's fill */
+static void peer_call(bcx *x, int p, int dir, const xg_msg *m, int64_t len)
+{
+    int64_t *fill = dir == OUT ? &x->soff : &x->rbase;
+    xg_p2p *q = ppush(&x->pp);
+    q->peer = p; q->is_send = dir == OUT; q->len = len;
+    if (m) { msg_end(x, m, dir, &q->buf, &q->off); return; }
+    q->buf = dir == OUT ? XG_BUF_STAGE_SEND : XG_BUF_STAGE_RECV; q->off = *fill;
+    *fill += len;
+}
+
+/* direct: one call per message, at its end on this GPU */
+static void direct_calls(bcx *x, int p, int dir)
+{
+    int k, hi;
+    for (k = peer_bucket(x, p, dir, &hi); k < hi; ++k) peer_call(x, p, dir, bk_msg(x, k), bk_msg(x, k)->len);
+}
+
+/* two-sided: one call of the whole list in staging; the receiver unpacks every message */
+static void two_sided_calls(bcx *x, int p, int dir)
+{
+    if (dir == IN) staged_copies(x, p, IN, x->rbase);
+    peer_call(x, p, dir, NULL, x->vol_b[dir * x->G + p]);
+}
+
+/* one-sided: one call per run, in staging where this end stages it (the receiver unpacks those),
+ * else where the run lies */
+static void one_sided_calls(bcx *x, int p, int dir)
+{
+    const oneside *o = &x->os[dir * x->G + p];
+    int r, k;
+    if (dir == IN) staged_copies(x, p, IN, x->rbase);
+    for (r = 0; r < o->nrun; ++r) {
+        int64_t len = 0;
+        for (k = o->run_b[r]; k < o->run_b[r + 1]; ++k) len += os_msg(x->s, o, k)->len;
+        peer_call(x, p, dir, os_staged(o, r, dir) ? NULL : os_msg(x->s, o, o->run_b[r]), len);
+    }
+}
+
+/* the grouped exchange: per peer, sends then receives, message order */
+static void step_calls(bcx *x, int b, int e, int relayed)
+{
+    int p, dir;
+    /* every message over all G - 1 links of its source, then of its destination (two groups) */
+    if (relayed && x->form == XG_RELAY) relay_calls(x, b, e);
+    for (p = 0; p < x->G; ++p)
+        for (dir = OUT; dir <= IN; ++dir) {
+            if (!x->vol_b[dir * x->G + p]) continue;
+            *(dir == OUT ? &x->dp->remote_send_bytes : &x->dp->remote_recv_bytes) += x->vol_b[dir * x->G + p];
+            if (relayed) continue;
+            if (!packed(x, p, dir)) direct_calls(x, p, dir);
+            else if (x->form == XG_PACK_ONE_SIDED) one_sided_calls(x, p, dir);
+            else two_sided_calls(x, p, dir);
+        }
+    if (!relayed && x->soff != x->sbase && !x->oom) { fprintf(stderr, "xg_devplan_build: staging mismatch\n"); abort(); }
 }
 
 xg_devplan *xg_devplan_build_form(const xg_sched *s, int ngpus, int g, int64_t pack_max_seg, int64_t pack_min,
                                   int form)
 {
-    xg_devplan *dp = (xg_devplan *)calloc(1, sizeof *dp);
-    int nst = s->nsteps, i, st, G = ngpus, oom = 0;
-    int *cnt = (int *)calloc(nst + 1, sizeof(int)), *order = (int *)malloc(sizeof(int) * (s->nmsg + 1));
-    int *pos = (int *)malloc(sizeof(int) * (nst + 1));
-    cvec pre, post;
-    pvec pp;
-    int64_t stage_s_max = 0, stage_r_max = 0;
-    int *bucket_n = (int *)calloc((size_t)G * 2, sizeof(int));
-    int64_t *bucket_b = (int64_t *)calloc((size_t)G * 2, sizeof(int64_t));
-    oneside *os_out = (oneside *)calloc((size_t)G, sizeof(oneside)), *os_in = (oneside *)calloc((size_t)G, sizeof(oneside));
-    int64_t *rl_e = (int64_t *)calloc((size_t)G, sizeof(int64_t)), *rl_i = (int64_t *)calloc((size_t)G, sizeof(int64_t));
-    int64_t *rl_p = (int64_t *)calloc((size_t)G * G, sizeof(int64_t));
-    int *rl_w = (int *)calloc((size_t)G * G * G, sizeof(int));       /* a weighted step's shares */
-    plan_bases pb;
-    memset(&pre, 0, sizeof pre); memset(&post, 0, sizeof post); memset(&pp, 0, sizeof pp);
-    memset(&pb, 0, sizeof pb);
-    if (form != XG_PACK_TWO_SIDED && form != XG_PACK_ONE_SIDED && form != XG_RELAY && form != XG_RELAY_COALESCED)
-        form = XG_PACK_FORM_DEFAULT;
-    if (form == XG_RELAY || form == XG_RELAY_COALESCED) pack_max_seg = 0;   /* every other step is direct */
-    if (!dp || !cnt || !order || !pos || !bucket_n || !bucket_b || !os_out || !os_in || !rl_e || !rl_i || !rl_p || !rl_w ||
-        plan_bases_init(&pb, s, G, g) ||
-        !(dp->steps = (xg_stepplan *)calloc(nst + 1, sizeof(xg_stepplan)))) {
-        oom = 1;
-        goto done;
-    }
+    const int nst = s->nsteps, G = ngpus;
+    int i, st;
+    xg_devplan *dp;
+    bcx x;
+    bcx_init(&x, s, G, g, pack_max_seg, pack_min, form);
+    dp = x.dp;
+    if (x.oom) goto done;
     dp->gpu = g; dp->ngpus = G; dp->nsteps = nst; dp->flags = xg_sched_ragged(s) ? XG_DP_RAGGED : 0;
-    {   /* per step, the request posts of this GPU's ranks (graph replays share their launch time
-         * out by them: xg_plan_run) */
-        int32_t *posts = (int32_t *)calloc((size_t)nst + 1, sizeof(int32_t));
-        if (!posts) { oom = 1; goto done; }
-        xgi_step_posts_of(s, G, g, posts, nst);
-        for (st = 0; st < nst; ++st) dp->steps[st].posts = posts[st];
-        free(posts);
-    }
+    /* per step, the request posts of this GPU's ranks (graph replays share their launch time out by
+     * them: xg_plan_run) */
+    xgi_step_posts_of(s, G, g, x.posts, nst);
+    for (st = 0; st < nst; ++st) dp->steps[st].posts = x.posts[st];
     /* in-loop MPI_Barrier -> device-side barrier after the step it completes at (G > 1) */
     for (i = 0; i < s->nbarrier; ++i)
         if (G > 1 && s->barrier_epoch[i] >= 0 && s->barrier_epoch[i] < nst) dp->steps[s->barrier_epoch[i]].sync_after = 1;
-    /* counting sort of messages by step, stable in message order */
-    for (i = 0; i < s->nmsg; ++i) cnt[s->msgs[i].step + 1]++;
-    for (st = 0; st < nst; ++st) cnt[st + 1] += cnt[st];
-    memcpy(pos, cnt, sizeof(int) * (nst + 1));
-    for (i = 0; i < s->nmsg; ++i) order[pos[s->msgs[i].step]++] = i;
     dp->region_bytes[XG_BUF_SEND] = xg_region_bytes(s, G, g, XG_BUF_SEND);
     dp->region_bytes[XG_BUF_RECV] = xg_region_bytes(s, G, g, XG_BUF_RECV);
     dp->region_bytes[XG_BUF_SCRATCH] = xg_region_bytes(s, G, g, XG_BUF_SCRATCH);
-    for (st = 0; st < nst; ++st) {
-        int b = cnt[st], e = cnt[st + 1], k, p, relayed, weighted;
-        int64_t sbase = 0, rbase = 0;
+    for (st = 0; st < nst && !x.oom; ++st) {
+        const int b = x.cnt[st], e = x.cnt[st + 1];
         xg_stepplan *sp = &dp->steps[st];
-        /* per-peer volume (out: [p], in: [G+p]) for the pack decision */
-        memset(bucket_n, 0, sizeof(int) * 2 * G);
-        memset(bucket_b, 0, sizeof(int64_t) * 2 * G);
-        sp->pre_begin = pre.n;
-        /* rank-local memcpy's through SCRATCH first, in a launch of their own: the
-         * local messages and packs below may read what they write in this step */
-        for (k = b; k < e; ++k) {
-            const xg_msg *m = &s->msgs[order[k]];
-            if (!moves(m) || !is_stage(m) || xg_gpu_of(s->P, G, m->src) != g) continue;
-            local_copy(cpush(&pre), &pb, m);
-            dp->local_bytes += m->len;
-        }
-        sp->stage_count = pre.n - sp->pre_begin;
-        for (k = b; k < e; ++k) {
-            const xg_msg *m = &s->msgs[order[k]];
-            int gs = xg_gpu_of(s->P, G, m->src), gd = xg_gpu_of(s->P, G, m->dst);
-            if (!moves(m) || is_stage(m)) continue;
-            if (gs == g && gd == g) {
-                local_copy(cpush(&pre), &pb, m);
-                dp->local_bytes += m->len;
-            } else if (gs == g) {
-                bucket_n[gd]++; bucket_b[gd] += m->len;
-            } else if (gd == g) {
-                bucket_n[G + gs]++; bucket_b[G + gs] += m->len;
-            }
-        }
-        sp->p2p_begin = pp.n;
-        sp->post_begin = post.n;
-        relayed = (form == XG_RELAY || form == XG_RELAY_COALESCED) && relay_step(s, order, b, e, G, rl_e, rl_i, rl_p);
-        weighted = 0;
-        if (!relayed && form == XG_RELAY_COALESCED) {
-            /* a step the uniform cut does not help may still take a weighted two-hop split */
-            const int ws = weighted_step(s, order, b, e, G, rl_w);
-            oom |= ws < 0;
-            weighted = ws > 0;
-        }
-        /* coalesced relay: its packs follow the local copies in the pre launch */
-        if ((relayed || weighted) && form == XG_RELAY_COALESCED)
-            oom |= relay_coalesced_calls(s, &pb, order, b, e, G, g, weighted ? rl_w : NULL, &pre, &pp, &post, &sbase,
-                                         &rbase) != 0;
-        relayed |= weighted;
-        /* the one-sided layout of every packed list of this GPU's, both directions */
-        if (form == XG_PACK_ONE_SIDED)
-            for (p = 0; p < G; ++p) {
-                if (p == g) continue;
-                if (bucket_n[p] && use_pack(bucket_n[p], bucket_b[p], pack_max_seg, pack_min))
-                    os_build(s, &pb, order, b, e, G, g, p, &os_out[p]);
-                if (bucket_n[G + p] && use_pack(bucket_n[G + p], bucket_b[G + p], pack_max_seg, pack_min))
-                    os_build(s, &pb, order, b, e, G, p, g, &os_in[p]);
-                oom |= os_out[p].fail | os_in[p].fail;
-            }
-        /* packs (into staging) join the pre-exchange copy launch */
-        for (p = 0; p < G; ++p) {
-            int64_t off = 0;
-            if (p == g || !bucket_n[p] || !use_pack(bucket_n[p], bucket_b[p], pack_max_seg, pack_min)) continue;
-            if (form == XG_PACK_ONE_SIDED) {
-                const oneside *o = &os_out[p];
-                int r;
-                for (r = 0; r < o->nrun; ++r) {
-                    if (o->by_src || !o->staged[r]) continue;     /* sent as it lies */
-                    for (k = o->run_b[r]; k < o->run_b[r + 1]; ++k) {
-                        const xg_msg *m = os_msg(s, o, k);
-                        xg_copy *c = cpush(&pre);
-                        c->src_buf = m->sbuf; c->src_off = src_off(&pb, m);
-                        c->dst_buf = XG_BUF_STAGE_SEND; c->dst_off = sbase + off;
-                        c->len = m->len;
-                        off += m->len;
-                    }
-                }
-                sbase += off;
-                continue;
-            }
-            for (k = b; k < e; ++k) {
-                const xg_msg *m = &s->msgs[order[k]];
-                if (!moves(m) || xg_gpu_of(s->P, G, m->src) != g || xg_gpu_of(s->P, G, m->dst) != p) continue;
-                {
-                    xg_copy *c = cpush(&pre);
-                    c->src_buf = m->sbuf; c->src_off = src_off(&pb, m);
-                    c->dst_buf = XG_BUF_STAGE_SEND; c->dst_off = sbase + off;
-                    c->len = m->len;
-                    off += m->len;
-                }
-            }
-            sbase += off;
-        }
-        sp->pre_count = pre.n - sp->pre_begin;
-        /* the grouped exchange: per peer, sends then receives, message order */
-        if (relayed) {
-            /* every message over all G - 1 links of its source, then of its destination (two groups) */
-            if (form == XG_RELAY) relay_calls(s, &pb, order, b, e, G, g, &pp, &rbase);
-            for (p = 0; p < G; ++p)
-                if (p != g) {
-                    dp->remote_send_bytes += bucket_b[p];
-                    dp->remote_recv_bytes += bucket_b[G + p];
-                }
-        } else {
-            int64_t soff = 0;
-            for (p = 0; p < G; ++p) {
-                int pk;
-                if (p == g) continue;
-                if (bucket_n[p]) {
-                    pk = use_pack(bucket_n[p], bucket_b[p], pack_max_seg, pack_min);
-                    if (pk && form == XG_PACK_ONE_SIDED) {
-                        const oneside *o = &os_out[p];
-                        int r;
-                        for (r = 0; r < o->nrun; ++r) {
-                            xg_p2p *q = ppush(&pp);
-                            int64_t len = 0;
-                            for (k = o->run_b[r]; k < o->run_b[r + 1]; ++k) len += os_msg(s, o, k)->len;
-                            q->peer = p; q->is_send = 1; q->len = len;
-                            if (!o->by_src && o->staged[r]) {
-                                q->buf = XG_BUF_STAGE_SEND; q->off = soff;
-                                soff += len;
-                            } else {
-                                const xg_msg *m = os_msg(s, o, o->run_b[r]);
-                                q->buf = m->sbuf; q->off = src_off(&pb, m);
-                            }
-                        }
-                    } else if (pk) {
-                        xg_p2p *o = ppush(&pp);
-                        o->peer = p; o->is_send = 1; o->buf = XG_BUF_STAGE_SEND; o->off = soff; o->len = bucket_b[p];
-                        soff += bucket_b[p];
-                    } else {
-                        for (k = b; k < e; ++k) {
-                            const xg_msg *m = &s->msgs[order[k]];
-                            if (!moves(m) || xg_gpu_of(s->P, G, m->src) != g || xg_gpu_of(s->P, G, m->dst) != p) continue;
-                            {
-                                xg_p2p *o = ppush(&pp);
-                                o->peer = p; o->is_send = 1; o->buf = m->sbuf;
-                                o->off = src_off(&pb, m); o->len = m->len;
-                            }
-                        }
-                    }
-                    dp->remote_send_bytes += bucket_b[p];
-                }
-                if (bucket_n[G + p]) {
-                    pk = use_pack(bucket_n[G + p], bucket_b[G + p], pack_max_seg, pack_min);
-                    if (pk && form == XG_PACK_ONE_SIDED) {
-                        const oneside *o = &os_in[p];
-                        int r;
-                        for (r = 0; r < o->nrun; ++r) {
-                            xg_p2p *q = ppush(&pp);
-                            int64_t len = 0;
-                            for (k = o->run_b[r]; k < o->run_b[r + 1]; ++k) len += os_msg(s, o, k)->len;
-                            q->peer = p; q->is_send = 0; q->len = len;
-                            if (o->by_src && o->staged[r]) {
-                                int64_t off = 0;
-                                q->buf = XG_BUF_STAGE_RECV; q->off = rbase;
-                                for (k = o->run_b[r]; k < o->run_b[r + 1]; ++k) {
-                                    const xg_msg *m = os_msg(s, o, k);
-                                    xg_copy *c = cpush(&post);
-                                    c->src_buf = XG_BUF_STAGE_RECV; c->src_off = rbase + off;
-                                    c->dst_buf = m->dbuf; c->dst_off = dst_off(&pb, m);
-                                    c->len = m->len;
-                                    off += m->len;
-                                }
-                                rbase += len;
-                            } else {
-                                const xg_msg *m = os_msg(s, o, o->run_b[r]);
-                                q->buf = m->dbuf; q->off = dst_off(&pb, m);
-                            }
-                        }
-                    } else if (pk) {
-                        xg_p2p *o = ppush(&pp);
-                        int64_t off = 0;
-                        o->peer = p; o->is_send = 0; o->buf = XG_BUF_STAGE_RECV; o->off = rbase; o->len = bucket_b[G + p];
-                        for (k = b; k < e; ++k) {
-                            const xg_msg *m = &s->msgs[order[k]];
-                            if (!moves(m) || xg_gpu_of(s->P, G, m->src) != p || xg_gpu_of(s->P, G, m->dst) != g) continue;
-                            {
-                                xg_copy *c = cpush(&post);
-                                c->src_buf = XG_BUF_STAGE_RECV; c->src_off = rbase + off;
-                                c->dst_buf = m->dbuf; c->dst_off = dst_off(&pb, m);
-                                c->len = m->len;
-                                off += m->len;
-                            }
-                        }
-                        rbase += bucket_b[G + p];
-                    } else {
-                        for (k = b; k < e; ++k) {
-                            const xg_msg *m = &s->msgs[order[k]];
-                            if (!moves(m) || xg_gpu_of(s->P, G, m->src) != p || xg_gpu_of(s->P, G, m->dst) != g) continue;
-                            {
-                                xg_p2p *o = ppush(&pp);
-                                o->peer = p; o->is_send = 0; o->buf = m->dbuf;
-                                o->off = dst_off(&pb, m); o->len = m->len;
-                            }
-                        }
-                    }
-                    dp->remote_recv_bytes += bucket_b[G + p];
-                }
-            }
-            if (soff != sbase && !oom) { fprintf(stderr, "xg_devplan_build: staging mismatch\n"); abort(); }
-        }
-        sp->p2p_count = pp.n - sp->p2p_begin;
-        sp->post_count = post.n - sp->post_begin;
-        if (sbase > stage_s_max) stage_s_max = sbase;
-        if (rbase > stage_r_max) stage_r_max = rbase;
-        for (p = 0; p < G; ++p) {
-            os_free(&os_out[p]);
-            os_free(&os_in[p]);
-        }
-        if (oom) goto done;
+        int relayed;
+        x.sbase = x.rbase = x.soff = 0;
+        sp->pre_begin = x.pre.n; sp->p2p_begin = x.pp.n; sp->post_begin = x.post.n;
+        step_index(&x, b, e);
+        step_stage_copies(&x, b, e);
+        sp->stage_count = x.pre.n - sp->pre_begin;
+        step_local_copies(&x);
+        relayed = step_relay(&x, b, e);
+        step_packs(&x, relayed);
+        sp->pre_count = x.pre.n - sp->pre_begin;
+        step_calls(&x, b, e, relayed);
+        sp->p2p_count = x.pp.n - sp->p2p_begin;
+        sp->post_count = x.post.n - sp->post_begin;
+        if (x.sbase > dp->region_bytes[XG_BUF_STAGE_SEND]) dp->region_bytes[XG_BUF_STAGE_SEND] = x.sbase;
+        if (x.rbase > dp->region_bytes[XG_BUF_STAGE_RECV]) dp->region_bytes[XG_BUF_STAGE_RECV] = x.rbase;
+        for (i = 0; i < 2 * G; ++i) os_free(&x.os[i]);
     }
     /* post copies are stored after the pre copies in one array */
-    oom |= pre.fail | post.fail | pp.fail;
-    dp->ncopy = pre.n + post.n;
-    if (!oom && (dp->copies = (xg_copy *)malloc(sizeof(xg_copy) * (dp->ncopy + 1)))) {
-        if (pre.n) memcpy(dp->copies, pre.v, sizeof(xg_copy) * pre.n);
-        if (post.n) memcpy(dp->copies + pre.n, post.v, sizeof(xg_copy) * post.n);
-        for (st = 0; st < nst; ++st) dp->steps[st].post_begin += pre.n;
-        dp->np2p = pp.n;
-        dp->p2p = pp.v ? pp.v : (xg_p2p *)malloc(sizeof(xg_p2p));
-        if (dp->p2p == pp.v) pp.v = NULL;           /* owned by the plan now */
-        dp->region_bytes[XG_BUF_STAGE_SEND] = stage_s_max;
-        dp->region_bytes[XG_BUF_STAGE_RECV] = stage_r_max;
+    x.oom |= x.pre.fail | x.post.fail | x.pp.fail;
+    dp->ncopy = x.pre.n + x.post.n;
+    if (!x.oom && (dp->copies = (xg_copy *)malloc(sizeof(xg_copy) * (dp->ncopy + 1)))) {
+        if (x.pre.n) memcpy(dp->copies, x.pre.v, sizeof(xg_copy) * x.pre.n);
+        if (x.post.n) memcpy(dp->copies + x.pre.n, x.post.v, sizeof(xg_copy) * x.post.n);
+        for (st = 0; st < nst; ++st) dp->steps[st].post_begin += x.pre.n;
+        dp->np2p = x.pp.n;
+        dp->p2p = x.pp.v ? (xg_p2p *)x.pp.v : (xg_p2p *)malloc(sizeof(xg_p2p));
+        if (dp->p2p == x.pp.v) x.pp.v = NULL;       /* owned by the plan now */
     }
-    oom |= !dp->copies || !dp->p2p;
+    x.oom |= !dp->copies || !dp->p2p;
 done:
-    free(pre.v); free(post.v); free(pp.v); free(cnt); free(order); free(pos); free(bucket_n); free(bucket_b);
-    free(os_out); free(os_in); free(rl_e); free(rl_i); free(rl_p); free(rl_w);
-    plan_bases_free(&pb);
-    if (oom) {
+    bcx_free(&x);
+    if (x.oom) {
         xg_devplan_free(dp);
         return NULL;
     }

@@ -3,7 +3,10 @@
  * plan form -- direct, two-sided, one-sided, relay, coalesced relay (uniform cuts, weighted splits,
  * large-piece calls) -- built for every GPU, proven to pair (xg_devplans_match), freed.  Built with
  * all host sources by tests/test_calls_fuzz.py under -fsanitize=address,undefined: out-of-bounds
- * piece bookkeeping, uninitialised shares or leaks in the builders abort the run. */
+ * piece bookkeeping, uninitialised shares or leaks in the builders abort the run.  It also prints,
+ * per form, a digest of every plan it built: the generator is seeded, so the jobs and -- as long as
+ * the builder produces the same plans -- the digests are the same in every build (the test pins
+ * those of the forms that use no libm). */
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -17,12 +20,52 @@ static int rnd(int n)
     return (int)(rng % (unsigned long long)n);
 }
 
+/* 64-bit FNV-1a over the fields of a plan, each fed as a fixed-width integer (never the structs'
+ * bytes: their padding is not defined) */
+static void fnv(uint64_t *h, uint64_t v)
+{
+    int i;
+    for (i = 0; i < 8; ++i, v >>= 8) *h = (*h ^ (v & 0xff)) * 1099511628211ull;
+}
+
+/* every field of xg_devplan, xg_stepplan, xg_copy and xg_p2p (xg_sched.h), counts included */
+static void digest_plan(uint64_t *h, const xg_devplan *p)
+{
+    int i;
+    fnv(h, (uint64_t)(int64_t)p->gpu); fnv(h, (uint64_t)(int64_t)p->ngpus);
+    fnv(h, (uint64_t)(int64_t)p->nsteps); fnv(h, (uint64_t)(int64_t)p->flags);
+    for (i = 0; i < XG_NBUF; ++i) fnv(h, (uint64_t)p->region_bytes[i]);
+    fnv(h, (uint64_t)(int64_t)p->ncopy); fnv(h, (uint64_t)(int64_t)p->np2p);
+    for (i = 0; i < p->ncopy; ++i) {
+        const xg_copy *c = &p->copies[i];
+        fnv(h, (uint64_t)c->src_off); fnv(h, (uint64_t)c->dst_off); fnv(h, (uint64_t)c->len);
+        fnv(h, (uint64_t)(int64_t)c->src_buf); fnv(h, (uint64_t)(int64_t)c->dst_buf);
+    }
+    for (i = 0; i < p->np2p; ++i) {
+        const xg_p2p *q = &p->p2p[i];
+        fnv(h, (uint64_t)q->off); fnv(h, (uint64_t)q->len);
+        fnv(h, (uint64_t)(int64_t)q->peer); fnv(h, (uint64_t)(int64_t)q->buf);
+        fnv(h, (uint64_t)(int64_t)q->is_send); fnv(h, (uint64_t)(int64_t)q->group);
+    }
+    for (i = 0; i < p->nsteps; ++i) {
+        const xg_stepplan *sp = &p->steps[i];
+        fnv(h, (uint64_t)(int64_t)sp->pre_begin); fnv(h, (uint64_t)(int64_t)sp->pre_count);
+        fnv(h, (uint64_t)(int64_t)sp->p2p_begin); fnv(h, (uint64_t)(int64_t)sp->p2p_count);
+        fnv(h, (uint64_t)(int64_t)sp->post_begin); fnv(h, (uint64_t)(int64_t)sp->post_count);
+        fnv(h, (uint64_t)(int64_t)sp->sync_after); fnv(h, (uint64_t)(int64_t)sp->stage_count);
+        fnv(h, (uint64_t)(int64_t)sp->posts);
+    }
+    fnv(h, (uint64_t)p->local_bytes); fnv(h, (uint64_t)p->remote_send_bytes); fnv(h, (uint64_t)p->remote_recv_bytes);
+}
+
 int main(int argc, char **argv)
 {
     static const int forms[][2] = {{0, -1}, {4 << 20, 0}, {4 << 20, 1}, {0, XG_RELAY}, {0, XG_RELAY_COALESCED}};
     static const long long sizes[] = {24, 4096, 65536 + 48, (1 << 20), (1 << 20) + 3, (2 << 20) + 5, (12 << 20) + 3};
     const int iters = argc > 1 ? atoi(argv[1]) : 200;
     int it, built = 0, refused = 0, relayed = 0;
+    uint64_t dig[5] = {1469598103934665603ull, 1469598103934665603ull, 1469598103934665603ull, 1469598103934665603ull,
+                       1469598103934665603ull};
     for (it = 0; it < iters; ++it) {
         const int P = 2 + rnd(39), A = 1 + rnd(P < 16 ? P : 16), G = 1 + rnd(P < 8 ? P : 8);
         const long long d = sizes[rnd(7)];
@@ -45,6 +88,7 @@ int main(int argc, char **argv)
             }
             for (g = 0; g < G; ++g) {
                 int st;
+                digest_plan(&dig[f], plans[g]);
                 for (st = 0; f >= 3 && g == 0 && st < plans[g]->nsteps; ++st) {
                     const xg_stepplan *sp = &plans[g]->steps[st];
                     int i;
@@ -58,5 +102,8 @@ int main(int argc, char **argv)
     }
     printf("ok after %d jobs: %d plan sets built, %d refused, %d second-group calls on GPU 0\n", iters, built, refused,
            relayed);
+    /* per form (forms[] order), over every plan built above */
+    printf("digests: %016llx %016llx %016llx %016llx %016llx\n", (unsigned long long)dig[0], (unsigned long long)dig[1],
+           (unsigned long long)dig[2], (unsigned long long)dig[3], (unsigned long long)dig[4]);
     return 0;
 }

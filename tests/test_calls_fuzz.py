@@ -37,3 +37,15 @@ def test_devplan_builders_fuzz_under_sanitizers(tmp_path):
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     assert "ok after 150 jobs" in p.stdout, p.stdout
+    digests = p.stdout.split("digests:")[1].split()
+    assert len(digests) == 5, p.stdout
+    assert digests[:4] == DEVPLAN_DIGESTS_150, p.stdout
+
+
+# FNV-1a digests of every field of every plan devplan_fuzz builds in its 150 jobs, per form: direct,
+# two-sided, one-sided, relay.  Recorded from the commit before devplan.c's builder was split into
+# one part per call form, so that refactors of it keep every plan; a change that is meant to alter
+# plans updates them.  The fifth digest (coalesced relay) is printed but not pinned: its weighted
+# steps run 1000 Frank-Wolfe iterations in doubles through libm's exp, and another machine's libm
+# may round a share differently.  (Forms 0-3 use integer arithmetic and IEEE basic operations only.)
+DEVPLAN_DIGESTS_150 = ["cf55ca464b38bfaa", "26b5ea71ee147be1", "100b7b59e7dc2265", "a3ecdad4f122ae5d"]
