@@ -67,6 +67,10 @@ int xg_is_virtual(const xg_ctx *ctx);                           /* 1 for a conte
  * step whose local part moves <= this many bytes lists it as self send/recv pairs in its RCCL
  * group (xg_devplan_step_calls).  The pairing proof of a job must use the same value. */
 int64_t xg_self_max(const xg_ctx *ctx);
+/* The plan knobs this context loads plans with (xg_sched.h: the device's facts, the defaults, the
+ * environment at xg_init, then rank / nranks / virt), copied to *out: a host-side table build
+ * (xg_plan_tables_build) under them gives this context's tables.  XG_EARG for a NULL argument. */
+int xg_ctx_knobs(const xg_ctx *ctx, xg_plan_knobs *out);
 int xg_barrier(xg_ctx *ctx);
 int xg_allreduce_max(xg_ctx *ctx, double *vals, int n);       /* in place, MAX over all GPUs (any n) */
 int xg_sync(xg_ctx *ctx);                                      /* this context's stream */

@@ -742,6 +742,14 @@ typedef struct xg_plan_knobs {
 /* What xg_init sets with an empty environment on a device of `cus` compute units that admits
  * engine_occ co-resident step-engine workgroups and wave_grid copy_kernel_w workgroups; rank 0 of 1. */
 void xg_plan_knobs_default(xg_plan_knobs *k, int cus, int engine_occ, int wave_grid);
+/* Apply the XG_* plan knobs found in env to k (already filled by xg_plan_knobs_default): the one
+ * place that reads them (xg_init calls it).  env: NULL-terminated array of
+ * "NAME=value" strings, first match of a name wins, as getenv; NULL: the process environment.
+ * Messages go to stderr: a refused XG_COPY_VARIANT, and, once per process, every retired knob
+ * still set. */
+void xg_plan_knobs_env(xg_plan_knobs *k, const char *const *env);
+/* The names it reads, in a fixed order; returns their number (out may be NULL). */
+int xg_plan_knob_names(const char **out, int cap);
 /* Build the tables of dp for regions of bytes[b] bytes at address base[b].  XG_EARG (with the
  * runtime's message on stderr) for a descriptor outside its region or a tile table that does not
  * cover its pieces; *out is then NULL. */

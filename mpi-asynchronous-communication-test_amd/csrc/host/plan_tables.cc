@@ -7,6 +7,7 @@
 
 #include <stdarg.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <string>
@@ -902,6 +903,121 @@ extern "C" void xg_plan_knobs_default(xg_plan_knobs *k, int cus, int engine_occ,
     k->fuse_stage = 1;
     k->split_after_pack = 1;
     k->nranks = 1;
+}
+
+// ---- the knobs' environment: the rules several variables share, then one row per variable.  v is
+// the variable's value, NULL when unset (atoi / atoll read "" and "abc" as 0, "1x" as 1).
+static void off_if_0(int32_t *f, const char *v) { *f = !(v && !strcmp(v, "0")); }     // off for exactly "0"; written even unset
+static void on_if_1(int32_t *f, const char *v) { *f = v && !strcmp(v, "1"); }         // on for exactly "1"; written even unset
+static void flag(int32_t *f, const char *v) { if (v) *f = atoi(v) != 0; }             // a set variable always writes
+static void number(int64_t *f, const char *v, int64_t lo = INT64_MIN) { if (v && atoll(v) >= lo) *f = atoll(v); }
+// a positive value lowers the field, never raises it
+static void cap(int32_t *f, const char *v) { if (v && atoi(v) > 0) *f = std::max(1, std::min(*f, atoi(v))); }
+
+struct Knob {
+    const char *name;
+    void (*apply)(xg_plan_knobs *k, const char *v);
+};
+#define KNOB(name, ...) {name, [](xg_plan_knobs *k, const char *v) { __VA_ARGS__; }}
+static const Knob kKnobs[] = {
+    KNOB("XG_COPY_VARIANT",                  // 0 by size (default), 1 plain, 6 non-temporal
+         if (v && (atoi(v) == 1 || atoi(v) == 6)) k->variant = atoi(v);
+         else if (v && atoi(v) != 0) fprintf(stderr, "xg: XG_COPY_VARIANT=%s ignored (0, 1 or 6)\n", v)),
+    // "0": a ragged plan's misaligned launches stay on copy_kernel_g (A/B)
+    KNOB("XG_RAGGED_COPY", if (v && atoi(v) == 0) k->rules.ragged_copy = 0),
+    // copy_kernel_x for a placement plan's launches of short extents (xg_copy_launch_choose): "0" keeps
+    // them on copy_kernel_s.  XG_EXTENT_MEAN_MAX / XG_EXTENT_TILE_KIB: the routing threshold and the
+    // tile's byte cap, for the A/B of profiles/extent_copy_ab.py
+    KNOB("XG_EXTENT_COPY", flag(&k->rules.extent_copy, v)),
+    KNOB("XG_EXTENT_MEAN_MAX", number(&k->rules.extent_mean_max, v, 1)),
+    KNOB("XG_EXTENT_TILE_KIB", if (v && atoi(v) > 0 && atoi(v) <= 1024) k->extent_tile = (int64_t)atoi(v) << 10),
+    // copy_kernel_q for large uniform launches (xg_copy_launch_choose): "0" restores copy_kernel_g's
+    // 32 KiB pieces.  XG_SMALL_PIECE_MIN: test hook, the launch size it starts at;
+    // XG_SMALL_PIECE_KIB (4 / 8) and XG_SMALL_PIECE_ORDER (copies per group of the piece order):
+    // for the A/B of profiles/small_pieces_ab.sh
+    KNOB("XG_SMALL_PIECES", flag(&k->rules.small_pieces, v)),
+    KNOB("XG_SMALL_PIECE_MIN", number(&k->rules.small_piece_min, v, 0)),
+    KNOB("XG_SMALL_PIECE_KIB", if (v && (atoi(v) == 4 || atoi(v) == 8)) k->rules.small_kib = atoi(v)),
+    KNOB("XG_SMALL_PIECE_ORDER", if (v && atoi(v) >= 1 && atoi(v) <= 1024) k->rules.small_order = atoi(v)),
+    KNOB("XG_ENGINE_MAX_STEP", number(&k->engine_max_step, v)),      // 0: never use the step engine
+    // test hook: a positive value caps the grid engine's workgroups (never raises them), so that a
+    // step's bytes are confined to a known number of CUs
+    KNOB("XG_ENGINE_WG", cap(&k->engine_wmax, v)),
+    KNOB("XG_ENGINE_DRAIN", on_if_1(&k->engine_drain, v)),           // "1": drain every step even without a hazard
+    KNOB("XG_ENGINE_SOLO", off_if_0(&k->solo, v)),                   // "0": never solo (the grid engine runs every segment)
+    KNOB("XG_ENGINE_SOLO_MAX", number(&k->solo_max, v)),
+    // waves per rail: 1 (default) or 16.  The rails' default follows the waves, so this row stands
+    // before XG_SOLO_RAILS'.  See DESIGN.md (solo engine): profiles/r02/rails/solo_probe.txt
+    KNOB("XG_SOLO_WAVES", k->solo_waves = v && atoi(v) == XG_SOLO_WAVES ? XG_SOLO_WAVES : 1;
+         k->solo_rails = k->solo_waves == 1 ? 512 : 16),             // 512 one-wave rails: 2 per CU by LDS
+    KNOB("XG_SOLO_RAILS", if (v && atoi(v) > 0) k->solo_rails = std::min(atoi(v), XG_SOLO_MAX_RAILS)),
+    KNOB("XG_COPY_LAUNCH_MAX", number(&k->launch_max, v)),           // bytes; 0 = one launch however large
+    // the wave-persistent copy for the launches of cross-GPU steps (packs, unpacks, the
+    // local part): profiles/r03/wave_copy/ -- one GPU's configs[2] pack launch 5.8 ->
+    // 6.25 TB/s; the 448 MiB non-temporal launches stay copy_kernel_g (6.0 vs 5.5-5.8);
+    // above kWaveMax the one-piece-per-workgroup launch is as fast or faster
+    // (profiles/r03/wave_local/: 28 MiB 9.3 vs 9.9 us, 56 MiB 18.7 vs 18.2, 112 MiB equal)
+    KNOB("XG_COPY_WAVE_MIN", number(&k->rules.wave_min, v)),         // test hook: 0 puts every cross-GPU launch on the wave copy
+    // test hook: a positive value caps the grid (never raises it), so that a wave gets several
+    // pieces -- on a whole device every launch of <= kWaveMax bytes has one piece per wave
+    KNOB("XG_WAVE_GRID", cap(&k->wave_grid, v)),
+    // piece KiB of a wave-copy launch: 0 = by its bytes (pieces.c), 2 / 4 / 8 forced (A/B)
+    KNOB("XG_WAVE_KIB", k->rules.wave_kib = v && (atoi(v) == 2 || atoi(v) == 4 || atoi(v) == 8) ? atoi(v) : 0),
+    KNOB("XG_STEP_CHAIN", off_if_0(&k->step_chain, v)),              // "0": a step mark after every step launch
+    // "1": arm single-segment plans (launched before the timed region, started by the host's
+    // doorbell ring).  Off by default: the reference's total_time brackets its request posts
+    // (mpi_test.c:1444, :1763), so the like-for-like time includes the kernel launch
+    KNOB("XG_ENGINE_ARM", on_if_1(&k->engine_arm, v)),
+    // a cross-GPU step's local part: <= self_max bytes travels in the step's RCCL group as self
+    // send/recv (one RCCL launch carries a latency-bound step), < split_min bytes joins the
+    // step's pack / fused launch, larger runs on the side stream beside the exchange (split).
+    // README configuration as a virtual 8-GPU job (profiles/r03/hybrid/): m6 direct 49 -> 2
+    // launches per run, m12 46 -> 6; configs[1..4]'s bulk local parts (MiBs) stay split
+    KNOB("XG_SPLIT_MIN", number(&k->split_min, v)),                  // bytes: a smaller local part is not split off
+    KNOB("XG_SELF_MAX", number(&k->self_max, v)),                    // bytes: local part posted as self send/recv (0: never)
+    KNOB("XG_FUSE_STAGE", off_if_0(&k->fuse_stage, v)),              // "0": stage copies always in a launch of their own
+    KNOB("XG_SPLIT_AFTER_PACK", off_if_0(&k->split_after_pack, v)),  // "0": a split step's local part and its packs start together
+};
+
+// name's value in env ("NAME=value" strings, the first match); env NULL: the process environment
+static const char *env_get(const char *const *env, const char *name)
+{
+    if (!env) return getenv(name);
+    const size_t n = strlen(name);
+    for (; *env; ++env)
+        if (!strncmp(*env, name, n) && (*env)[n] == '=') return *env + n + 1;
+    return nullptr;
+}
+
+// Knobs that are constants now (Knobs): a setting left in the environment -- an A/B
+// recipe under profiles/ from the round that measured it -- changes nothing, so say so once
+static void warn_folded_knobs(const char *const *env)
+{
+    static bool done = false;
+    if (done) return;
+    done = true;
+    static const char *const folded[] = {
+        // round 4: settled tuning
+        "XG_COPY_BALANCE", "XG_COPY_CHUNK", "XG_COPY_NT_MIN", "XG_COPY_NT_STREAM", "XG_COPY_WAVE",
+        "XG_COPY_WAVE_MAX", "XG_COPY_WG_COST", "XG_FUSE_UNPACK", "XG_GRID_CACHE_MAX",
+        "XG_PIECE_ORDER", "XG_SOLO_MIN_STEPS", "XG_SOLO_RELAY", "XG_SPLIT_LOCAL",
+        // round 5: environment twins of bin/test options (--fingerprint, --eager-limit, ...)
+        "XG_FINGERPRINT", "XG_EAGER_LIMIT", "XG_PACK_MAX_SEG", "XG_PACK_MIN", "XG_PACK_FORM"};
+    for (const char *k : folded)
+        if (env_get(env, k)) fprintf(stderr, "xg: %s is set but no longer read (folded into a constant or an option)\n", k);
+}
+
+extern "C" void xg_plan_knobs_env(xg_plan_knobs *k, const char *const *env)
+{
+    warn_folded_knobs(env);
+    for (const Knob &r : kKnobs) r.apply(k, env_get(env, r.name));
+}
+
+extern "C" int xg_plan_knob_names(const char **out, int cap)
+{
+    const int n = (int)(sizeof kKnobs / sizeof *kKnobs);
+    for (int i = 0; out && i < n && i < cap; ++i) out[i] = kKnobs[i].name;
+    return n;
 }
 
 extern "C" int xg_plan_tables_build(const xg_devplan *dp, const xg_plan_knobs *k, const uint64_t base[XG_NBUF],

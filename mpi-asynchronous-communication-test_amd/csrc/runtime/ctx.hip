@@ -166,32 +166,14 @@ extern "C" int xg_init(xg_ctx **out, int rank, int nranks, int device, const voi
     return XG_OK;
 }
 
-// Knobs that are constants now (Knobs): a setting left in the environment -- an A/B
-// recipe under profiles/ from the round that measured it -- changes nothing, so say so once
-static void warn_folded_knobs()
-{
-    static bool done = false;
-    if (done) return;
-    done = true;
-    static const char *const folded[] = {
-        // round 4: settled tuning
-        "XG_COPY_BALANCE", "XG_COPY_CHUNK", "XG_COPY_NT_MIN", "XG_COPY_NT_STREAM", "XG_COPY_WAVE",
-        "XG_COPY_WAVE_MAX", "XG_COPY_WG_COST", "XG_FUSE_UNPACK", "XG_GRID_CACHE_MAX",
-        "XG_PIECE_ORDER", "XG_SOLO_MIN_STEPS", "XG_SOLO_RELAY", "XG_SPLIT_LOCAL",
-        // round 5: environment twins of bin/test options (--fingerprint, --eager-limit, ...)
-        "XG_FINGERPRINT", "XG_EAGER_LIMIT", "XG_PACK_MAX_SEG", "XG_PACK_MIN", "XG_PACK_FORM"};
-    for (const char *k : folded)
-        if (getenv(k)) fprintf(stderr, "xg: %s is set but no longer read (folded into a constant or an option)\n", k);
-}
-
 // the rest of xg_init: tuning knobs, streams, scratch, the communicator
 static int init_ctx(xg_ctx *c, const void *uid)
 {
-    warn_folded_knobs();
     const int device = c->device, rank = c->rank, nranks = c->nranks;
     // The plan-table knobs (xg_plan_knobs, the context's base): the device's facts, the defaults
     // (xg_plan_knobs_default, plan_tables.cc -- each default's measurement is named there), then the
-    // environment.  The engine's grid barrier needs every workgroup resident at once: engine_occ.
+    // environment (xg_plan_knobs_env, beside it: one row per XG_* knob, and the warning about retired
+    // ones).  The engine's grid barrier needs every workgroup resident at once: engine_occ.
     {
         int cus = 0, per_cu = 0, w_per_cu = 0;
         HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
@@ -200,94 +182,13 @@ static int init_ctx(xg_ctx *c, const void *uid)
                                                             0));
         c->engine_occ = cus * (per_cu < 1 ? 1 : per_cu);
         xg_plan_knobs_default(c, cus, c->engine_occ, (cus > 0 ? cus : 256) * (w_per_cu < 1 ? 1 : w_per_cu));
+        xg_plan_knobs_env(c, nullptr);
         c->rank = rank; c->nranks = nranks;
     }
     c->kt_mode = 0; c->nk = 0; c->kt_bytes = 0;
-    const char *env = getenv("XG_COPY_VARIANT");          // 0 by size (default), 1 plain, 6 non-temporal
-    if (env && (atoi(env) == 1 || atoi(env) == 6)) c->variant = atoi(env);
-    else if (env && atoi(env) != 0) fprintf(stderr, "xg: XG_COPY_VARIANT=%s ignored (0, 1 or 6)\n", env);
-    env = getenv("XG_RAGGED_COPY");          // "0": a ragged plan's misaligned launches stay on copy_kernel_g (A/B)
-    if (env && atoi(env) == 0) c->rules.ragged_copy = 0;
-    // copy_kernel_x for a placement plan's launches of short extents (xg_copy_launch_choose): "0" keeps
-    // them on copy_kernel_s.  XG_EXTENT_MEAN_MAX / XG_EXTENT_TILE_KIB: the routing threshold and the
-    // tile's byte cap, for the A/B of profiles/extent_copy_ab.py
-    env = getenv("XG_EXTENT_COPY");
-    if (env) c->rules.extent_copy = atoi(env) != 0;
-    env = getenv("XG_EXTENT_MEAN_MAX");
-    if (env && atol(env) > 0) c->rules.extent_mean_max = atol(env);
-    env = getenv("XG_EXTENT_TILE_KIB");
-    if (env && atoi(env) > 0 && atoi(env) <= 1024) c->extent_tile = (int64_t)atoi(env) << 10;
-    // copy_kernel_q for large uniform launches (xg_copy_launch_choose): "0" restores copy_kernel_g's
-    // 32 KiB pieces.  XG_SMALL_PIECE_MIN: test hook, the launch size it starts at;
-    // XG_SMALL_PIECE_KIB (4 / 8) and XG_SMALL_PIECE_ORDER (copies per group of the piece order):
-    // for the A/B of profiles/small_pieces_ab.sh
-    env = getenv("XG_SMALL_PIECES");
-    if (env) c->rules.small_pieces = atoi(env) != 0;
-    env = getenv("XG_SMALL_PIECE_MIN");
-    if (env && atoll(env) >= 0) c->rules.small_piece_min = atoll(env);
-    env = getenv("XG_SMALL_PIECE_KIB");
-    if (env && (atoi(env) == 4 || atoi(env) == 8)) c->rules.small_kib = atoi(env);
-    env = getenv("XG_SMALL_PIECE_ORDER");
-    if (env && atoi(env) >= 1 && atoi(env) <= 1024) c->rules.small_order = atoi(env);
-    env = getenv("XG_ENGINE_MAX_STEP");      // 0: never use the step engine
-    if (env) c->engine_max_step = atol(env);
-    // test hook: a positive value caps the grid engine's workgroups (never raises them), so that a
-    // step's bytes are confined to a known number of CUs
-    env = getenv("XG_ENGINE_WG");
-    if (env && atoi(env) > 0) c->engine_wmax = std::max(1, std::min(c->engine_wmax, atoi(env)));
-    env = getenv("XG_ENGINE_DRAIN");         // "1": drain every step even without a hazard
-    c->engine_drain = env && !strcmp(env, "1");
-    env = getenv("XG_ENGINE_SOLO");          // "0": never solo (the grid engine runs every segment)
-    c->solo = !(env && !strcmp(env, "0"));
-    env = getenv("XG_ENGINE_SOLO_MAX");
-    if (env) c->solo_max = atol(env);
-    env = getenv("XG_SOLO_WAVES");           // waves per rail: 1 (default) or 16
-    c->solo_waves = env && atoi(env) == xgk::kSoloWaves ? xgk::kSoloWaves : 1;
-    // see DESIGN.md (solo engine): profiles/r02/rails/solo_probe.txt
-    c->solo_rails = c->solo_waves == 1 ? 512 : 16;     // 512 one-wave rails: 2 per CU by LDS
-    env = getenv("XG_SOLO_RAILS");
-    if (env && atoi(env) > 0) c->solo_rails = std::min(atoi(env), xgk::kSoloMaxRails);
-    env = getenv("XG_COPY_LAUNCH_MAX");      // bytes; 0 = one launch however large
-    if (env) c->launch_max = atoll(env);
-    {
-        // the wave-persistent copy for the launches of cross-GPU steps (packs, unpacks, the
-        // local part): profiles/r03/wave_copy/ -- one GPU's configs[2] pack launch 5.8 ->
-        // 6.25 TB/s; the 448 MiB non-temporal launches stay copy_kernel_g (6.0 vs 5.5-5.8);
-        // above kWaveMax the one-piece-per-workgroup launch is as fast or faster
-        // (profiles/r03/wave_local/: 28 MiB 9.3 vs 9.9 us, 56 MiB 18.7 vs 18.2, 112 MiB equal)
-        env = getenv("XG_COPY_WAVE_MIN");     // test hook: 0 puts every cross-GPU launch on the wave copy
-        if (env) c->rules.wave_min = atoll(env);
-        // test hook: a positive value caps the grid (never raises it), so that a wave gets several
-        // pieces -- on a whole device every launch of <= kWaveMax bytes has one piece per wave
-        env = getenv("XG_WAVE_GRID");
-        if (env && atoi(env) > 0) c->wave_grid = std::max(1, std::min(c->wave_grid, atoi(env)));
-        // piece KiB of a wave-copy launch: 0 = by its bytes (pieces.c), 2 / 4 / 8 forced (A/B)
-        env = getenv("XG_WAVE_KIB");
-        c->rules.wave_kib = env && (atoi(env) == 2 || atoi(env) == 4 || atoi(env) == 8) ? atoi(env) : 0;
-    }
-    env = getenv("XG_STEP_CHAIN");           // "0": a step mark after every step launch
-    c->step_chain = !(env && !strcmp(env, "0"));
-    // "1": arm single-segment plans (launched before the timed region, started by the host's
-    // doorbell ring).  Off by default: the reference's total_time brackets its request posts
-    // (mpi_test.c:1444, :1763), so the like-for-like time includes the kernel launch
-    env = getenv("XG_ENGINE_ARM");
-    c->engine_arm = env && !strcmp(env, "1");
-    // a cross-GPU step's local part: <= self_max bytes travels in the step's RCCL group as self
-    // send/recv (one RCCL launch carries a latency-bound step), < split_min bytes joins the
-    // step's pack / fused launch, larger runs on the side stream beside the exchange (split).
-    // README configuration as a virtual 8-GPU job (profiles/r03/hybrid/): m6 direct 49 -> 2
-    // launches per run, m12 46 -> 6; configs[1..4]'s bulk local parts (MiBs) stay split
-    env = getenv("XG_SPLIT_MIN");            // bytes: a smaller local part is not split off
-    if (env) c->split_min = atoll(env);
-    env = getenv("XG_SELF_MAX");             // bytes: local part posted as self send/recv (0: never)
-    if (env) c->self_max = atoll(env);
-    env = getenv("XG_FUSE_STAGE");           // "0": stage copies always in a launch of their own
-    c->fuse_stage = !(env && !strcmp(env, "0"));
-    env = getenv("XG_SPLIT_AFTER_PACK");     // "0": a split step's local part and its packs start together
-    c->split_after_pack = !(env && !strcmp(env, "0"));
     // hipGraph replay: "1" every multi-launch run (and virtual job), "0" never; default (-1):
     // one-GPU latency-bound runs only (xg_plan.graph_auto)
-    env = getenv("XG_GRAPH");
+    const char *env = getenv("XG_GRAPH");
     c->graph = env ? (!strcmp(env, "1") ? 1 : 0) : -1;
     {
         int khz = 0;
@@ -367,6 +268,13 @@ extern "C" int xg_finalize(xg_ctx *c)
 extern "C" int xg_rank(const xg_ctx *c) { return c->rank; }
 extern "C" int xg_nranks(const xg_ctx *c) { return c->nranks; }
 extern "C" int64_t xg_self_max(const xg_ctx *c) { return c ? c->self_max : 0; }
+
+extern "C" int xg_ctx_knobs(const xg_ctx *c, xg_plan_knobs *out)
+{
+    if (!c || !out) return XG_EARG;
+    memcpy(out, static_cast<const xg_plan_knobs *>(c), sizeof *out);
+    return XG_OK;
+}
 
 extern "C" int xg_sync(xg_ctx *c)
 {

@@ -168,8 +168,9 @@ class PlanTables:
     """The tables xg_plan_load builds from a device plan, built with no GPU (xg_plan_tables_build,
     csrc/host/plan_tables.cc).  dp: a DevPlan (or a pointer to one); base / nbytes: the regions'
     addresses and sizes (default: 2 MiB-aligned fake addresses, the plan's own region sizes);
-    cus / engine_occ / wave_grid: the device facts xg_init queries (default: a whole MI355X);
-    knobs: xg_plan_knobs or xg_copy_rules fields by name, over xg_plan_knobs_default."""
+    cus / engine_occ / wave_grid: the device facts xg_init queries (default: a whole MI355X; a
+    context's own: Context.knobs()); env: the XG_* knobs a context would be opened under;
+    knobs: xg_plan_knobs or xg_copy_rules fields by name, over both."""
     _lib = None
 
     @classmethod
@@ -179,6 +180,9 @@ class PlanTables:
             T, I = C.c_void_p, C.POINTER(C.c_int)
             h.xg_plan_knobs_default.restype = None
             h.xg_plan_knobs_default.argtypes = [C.POINTER(PlanKnobs), C.c_int, C.c_int, C.c_int]
+            h.xg_plan_knobs_env.restype = None
+            h.xg_plan_knobs_env.argtypes = [C.POINTER(PlanKnobs), C.POINTER(C.c_char_p)]
+            h.xg_plan_knob_names.argtypes = [C.POINTER(C.c_char_p), C.c_int]
             h.xg_plan_tables_build.argtypes = [C.POINTER(DevPlan), C.POINTER(PlanKnobs), C.POINTER(C.c_uint64),
                                                C.POINTER(C.c_int64), C.POINTER(T)]
             h.xg_plan_tables_free.restype = None
@@ -196,22 +200,37 @@ class PlanTables:
         return cls._lib
 
     @classmethod
-    def knobs(cls, cus=256, engine_occ=256, wave_grid=2048, **over):
+    def knob_names(cls):
+        """the environment variables xg_plan_knobs_env reads"""
+        out = (C.c_char_p * cls.lib().xg_plan_knob_names(None, 0))()
+        cls.lib().xg_plan_knob_names(out, len(out))
+        return [n.decode() for n in out]
+
+    @classmethod
+    def knobs(cls, cus=256, engine_occ=256, wave_grid=2048, env=None, **over):
+        """the defaults, then env ({name: value}, parsed as xg_init parses the process environment, which
+        is not touched; XG_GRAPH is no plan knob and passes, another unknown name raises), then over"""
         k = PlanKnobs()
         cls.lib().xg_plan_knobs_default(C.byref(k), cus, engine_occ, wave_grid)
+        if env is not None:
+            unknown = set(env) - set(cls.knob_names()) - {"XG_GRAPH"}
+            if unknown:
+                raise XGError("not a plan knob: %s" % ", ".join(sorted(unknown)))
+            arr = [("%s=%s" % nv).encode() for nv in env.items()] + [None]
+            cls.lib().xg_plan_knobs_env(C.byref(k), (C.c_char_p * len(arr))(*arr))
         rules = set(f[0] for f in CopyRules._fields_)
         for name, v in over.items():
             setattr(k.rules if name in rules else k, name, v)      # an unknown name raises (ctypes structures take no new fields)
             assert name in rules or name in set(f[0] for f in PlanKnobs._fields_), name
         return k
 
-    def __init__(self, dp, base=None, nbytes=None, cus=256, engine_occ=256, wave_grid=2048, **knobs):
+    def __init__(self, dp, base=None, nbytes=None, cus=256, engine_occ=256, wave_grid=2048, env=None, **knobs):
         h = self.lib()
         dpp = dp if isinstance(dp, C.POINTER(DevPlan)) else C.pointer(dp)
         self.base = list(base) if base is not None else [(b + 1) << 40 for b in range(NBUF)]
         self.nbytes = list(nbytes) if nbytes is not None else list(dpp.contents.region_bytes)
         self.h = C.c_void_p()
-        k = self.knobs(cus, engine_occ, wave_grid, **knobs)
+        k = self.knobs(cus, engine_occ, wave_grid, env, **knobs)
         rc = h.xg_plan_tables_build(dpp, C.byref(k), (C.c_uint64 * NBUF)(*self.base), (C.c_int64 * NBUF)(*self.nbytes),
                                     C.byref(self.h))
         if rc:
@@ -1160,6 +1179,7 @@ def device():
         d.xg_plan_set_step_marks.argtypes = [vp, C.POINTER(C.c_uint8)]
         d.xg_self_max.restype = i64
         d.xg_self_max.argtypes = [vp]
+        d.xg_ctx_knobs.argtypes = [vp, C.POINTER(PlanKnobs)]
         d.xg_barrier.argtypes = [vp]
         d.xg_sync.argtypes = [vp]
         d.xg_device_sync.argtypes = [vp]
@@ -1272,6 +1292,12 @@ class Context:
     @property
     def handle(self):
         return self._c
+
+    def knobs(self):
+        """the PlanKnobs this context loads plans with (xg_ctx_knobs)"""
+        k = PlanKnobs()
+        _check(_dev.xg_ctx_knobs(self._c, C.byref(k)), "xg_ctx_knobs")
+        return k
 
     def barrier(self):
         _check(_dev.xg_barrier(self._c), "xg_barrier")

@@ -185,16 +185,6 @@ CASES = {
 BACK_TO_BACK = [c for c in CASES if c != "cut"]         # the cases of every sequence; "cut": the per-launch session only
 
 
-def knobs(env):
-    """the xg_plan_knobs / xg_copy_rules fields xg_init sets from these environment variables, for
-    xg.PlanTables (time_plan.knobs, and the two knobs only these cases use)"""
-    from time_plan import knobs as base
-    more = dict(XG_SMALL_PIECE_MIN="small_piece_min", XG_COPY_LAUNCH_MAX="launch_max")
-    k = base({n: v for n, v in env.items() if n not in more})
-    k.update({more[n]: v for n, v in env.items() if n in more})
-    return k
-
-
 def form(records, kinds):
     """time_plan.form of a plan's tables (xg.parse_tables), with graph_auto, the launches per kernel
     kind (kinds: xg_plan_kind_launches of the loaded plan, PlanTables.kind_launches of a host build:

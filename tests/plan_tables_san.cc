@@ -2,11 +2,14 @@
 // csrc/host/plan_tables.cc and the C host sources under -fsanitize=address,undefined and runs it):
 // builds the plan tables of a handful of device plans and checks, in C++ over the tables
 // themselves, that every positive copy is covered exactly once by the pieces and rows of its step's
-// launches (or, deferred, of the next step's launch that holds the previous unpacks).
+// launches (or, deferred, of the next step's launch that holds the previous unpacks).  It also drives
+// the knobs' environment parser (xg_plan_knobs_env) with scripted arrays.
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <map>
+#include <string>
 #include <tuple>
 #include <vector>
 
@@ -105,6 +108,57 @@ static void check_cover(const xg_devplan *dp, const PlanKnobs *k)
     ++g_plans;
 }
 
+// xg_plan_knobs_env over scripted environments.  Every entry is a heap string of its exact length,
+// so a read past an entry's end (a name longer than the entry, an entry without '=') is the
+// sanitizer's to find.  -> the number of environments read
+static int knob_environments()
+{
+    snprintf(g_what, sizeof g_what, "knob environments");
+    const int nn = xg_plan_knob_names(nullptr, 0);
+    std::vector<const char *> names((size_t)nn);
+    CHECK(nn > 20 && xg_plan_knob_names(names.data(), nn) == nn);
+    const std::string nines(1 << 20, '9');
+    std::vector<std::string> all;
+    for (const char *n : names) all.push_back(std::string(n) + "=1");
+    const std::vector<std::vector<std::string>> envs = {
+        {},
+        {"XG_SELF_MAX=" + nines, "XG_ENGINE_SOLO=0" + nines, "XG_WAVE_KIB=" + std::string(1 << 20, ' ') + "8"},
+        {"XG_ENGINE_WG=99999999999", "XG_SOLO_RAILS=99999999999", "XG_SMALL_PIECE_ORDER=4294967297",
+         "XG_EXTENT_TILE_KIB=4294967297", "XG_SPLIT_MIN=99999999999"},
+        {"XG_SELF_MAX", "XG_SELF_MA", "X", "", "XG_SELF_MAX=3"},
+        {"=5", "==", "=XG_SELF_MAX=4", "XG_SELF_MAX=6"},
+        all,
+        {"XG_STEP_CHAIN=0", "XG_STEP_CHAIN=1", "XG_SELF_MAX=7", "XG_SELF_MAX=8"},
+        {"XG_COPY_CHUNK=1", "XG_COPY_VARIANT=0"},                 // a retired name: one line on stderr
+    };
+    int read = 0;
+    for (const auto &e : envs) {
+        std::vector<char *> arr;
+        for (const std::string &s : e) arr.push_back(strdup(s.c_str()));
+        arr.push_back(nullptr);
+        xg_plan_knobs k, d;
+        xg_plan_knobs_default(&k, 256, 256, 2048);
+        xg_plan_knobs_default(&d, 256, 256, 2048);
+        xg_plan_knobs_env(&k, arr.data());
+        for (char *s : arr) free(s);
+        CHECK(k.engine_wmax >= 1 && k.engine_wmax <= 256 && k.solo_rails >= 1 && k.solo_rails <= XG_SOLO_MAX_RAILS);
+        CHECK(k.rules.small_order >= 1 && k.rules.small_order <= 1024 && k.extent_tile >= 1024 && k.extent_tile <= 1 << 20);
+        switch (read) {
+        case 0: CHECK(!memcmp(&k, &d, sizeof k)); break;
+        case 1: CHECK(k.self_max == INT64_MAX && k.solo == 1 && k.rules.wave_kib == 8); break;
+        case 2: CHECK(k.split_min == 99999999999ll); break;
+        case 3: CHECK(k.self_max == 3); break;
+        case 4: CHECK(k.self_max == 6); break;
+        case 5: CHECK(k.variant == 1 && k.engine_wmax == 1 && k.wave_grid == 1 && k.solo_rails == 1 && k.self_max == 1 &&
+                      k.extent_tile == 1024 && k.engine_drain == 1 && k.engine_arm == 1 && k.rules.wave_kib == 0); break;
+        case 6: CHECK(k.step_chain == 0 && k.self_max == 7); break;
+        default: CHECK(!memcmp(&k, &d, sizeof k)); break;
+        }
+        ++read;
+    }
+    return read;
+}
+
 int main()
 {
     PlanKnobs k;
@@ -177,6 +231,7 @@ int main()
             xg_sched_free(s);
         }
     }
+    printf("knob environments: %d read\n", knob_environments());
     printf("%d plans covered\n", g_plans);
     return g_plans > 100 ? 0 : 1;
 }

@@ -66,7 +66,7 @@ def _assert_routing(xg, case, which, sy, pp):
     # the dispatches of a run and their bytes: the loaded tables and the host's own build agree
     dp = devplan(xg, sy.steps, pp.send_bytes, pp.recv_bytes)
     dp.flags = pp.flags
-    pt = xg.PlanTables(dp, **PP.knobs(c["env"]))
+    pt = xg.PlanTables(dp, env=c["env"])
     try:
         disp = PP.dispatch_bytes(pt.records())
     finally:

@@ -101,7 +101,7 @@ def test_routing(xg, case, which):
     steps = pp.steps_a if which == "a" else pp.steps_b
     dp = devplan(xg, steps, pp.send_bytes, pp.recv_bytes)
     dp.flags = pp.flags
-    pt = xg.PlanTables(dp, **PP.knobs(c["env"]))
+    pt = xg.PlanTables(dp, env=c["env"])
     try:
         rec = pt.records()
         f = PP.form(rec, pt.kind_launches())
@@ -124,7 +124,7 @@ def test_cut_case_has_unequal_dispatches(xg):
     c, pp = PP.CASES["cut"], _pp("cut")
     for steps in (pp.steps_a, pp.steps_b):
         dp = devplan(xg, steps, pp.send_bytes, pp.recv_bytes)
-        pt = xg.PlanTables(dp, **PP.knobs(c["env"]))
+        pt = xg.PlanTables(dp, env=c["env"])
         try:
             rec = pt.records()
             cutl = [l for l in rec["launch"] if l["ndisp"] > 1]

@@ -550,8 +550,10 @@ def test_default_knobs_are_the_rules_defaults(xg):
 def test_plan_tables_under_sanitizers(tmp_path):
     """tests/plan_tables_san.cc (its own main) builds the tables of a handful of plans -- golden-like
     schedules on 1, 2 and 8 GPUs in every pack form, a ragged one, a placement plan, cut at several
-    launch_max -- and checks the cover property in C++, compiled with plan_tables.cc and the C host
-    sources under AddressSanitizer and UBSan and run as an executable"""
+    launch_max -- and checks the cover property in C++, then reads scripted knob environments (empty,
+    very long values, digits past int, entries without '=', an empty name, every variable at once),
+    compiled with plan_tables.cc and the C host sources under AddressSanitizer and UBSan and run as
+    an executable"""
     host = os.path.join(PKG, "csrc", "host")
     inc = ["-I" + os.path.join(os.path.dirname(HERE), "include")]
     san = ["-g", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
@@ -568,6 +570,7 @@ def test_plan_tables_under_sanitizers(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])
     assert "plans covered" in out.stdout, out.stdout
+    assert "knob environments: 8 read" in out.stdout, out.stdout         # its xg_plan_knobs_env section
 
 
 if __name__ == "__main__":

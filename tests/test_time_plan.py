@@ -70,7 +70,7 @@ def test_further_plans_take_the_expected_form(xg):
     for job, spec, want in ((T.job_cross(), T.V_CROSS, T.V_CROSS_FORM), (T.job_segment(), T.V_SEG, T.V_SEG_FORM)):
         job.check()
         for g in range(2):
-            pt = xg.PlanTables(job.devplan(xg, g), **dict(T.knobs(spec["env"]), rank=g, nranks=2, virt=1))
+            pt = xg.PlanTables(job.devplan(xg, g), env=spec["env"], rank=g, nranks=2, virt=1)
             try:
                 rec = pt.records()
             finally:

@@ -117,25 +117,6 @@ ROUTES = {
 CASES = [(r, pos) for r in ROUTES for pos in POSITIONS]
 
 
-def knobs(env):
-    """the xg_plan_knobs fields xg_init sets from these environment variables (ctx.hip) on a
-    256-CU device, for xg.PlanTables"""
-    k = {}
-    names = dict(XG_ENGINE_MAX_STEP="engine_max_step", XG_STEP_CHAIN="step_chain", XG_ENGINE_SOLO="solo",
-                 XG_ENGINE_ARM="engine_arm", XG_SOLO_RAILS="solo_rails", XG_SPLIT_MIN="split_min",
-                 XG_SELF_MAX="self_max")
-    if env.get("XG_SOLO_WAVES") == 16:
-        k["solo_waves"], k["solo_rails"] = 16, 16
-    for name, v in env.items():
-        if name in names:
-            k[names[name]] = v
-        elif name == "XG_ENGINE_WG":
-            k["engine_wmax"] = min(256, v)
-        else:
-            assert name in ("XG_SOLO_WAVES", "XG_GRAPH"), name
-    return k
-
-
 def sized(route, pos):
     """the route's plan with the heavy step at `pos` -> (steps, send_bytes, recv_bytes, p)"""
     r = ROUTES[route]
@@ -166,7 +147,7 @@ def form(records):
 
 def expected_form(route, nsteps):
     """the form the route's plan must take, stated by hand: what the GPU test asserts of the loaded
-    plan and test_time_plan.py of xg.PlanTables under knobs(env)"""
+    plan and test_time_plan.py of xg.PlanTables under env"""
     r = ROUTES[route]
     n = nsteps - (1 if r.get("tail") else 0)          # the segment's steps
     kind, env = r["kind"], r["env"]
@@ -249,8 +230,8 @@ def devplan(xg, steps, send_bytes, recv_bytes):
 
 
 def tables_form(xg, dp, env, **more):
-    """form() of the tables xg.PlanTables builds for dp under knobs(env) on a 256-CU device"""
-    pt = xg.PlanTables(dp, **dict(knobs(env), **more))
+    """form() of the tables xg.PlanTables builds for dp under env on a 256-CU device"""
+    pt = xg.PlanTables(dp, env=env, **more)
     try:
         return form(pt.records())
     finally:
