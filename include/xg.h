@@ -228,6 +228,16 @@ int xg_vplans_run_rccl(xg_plan *const *plans, int n, double *step_done);
  * keep the poison) -- so one GPU's share of a job too large to emulate whole on one device
  * executes at full size.  XG_EARG for a non-virtual context or a plan with self calls. */
 int xg_plan_set_local_only(xg_plan *p, int on);
+/* Test hook: start the plan's engine counters anywhere.  The step engines' state holds cumulative
+ * 32-bit counters that no launch resets (xg_sched.h xg_eng_*); this makes it exactly what earlier
+ * launches would have left that took `tickets` grid-barrier tickets in all, `armed` of them armed
+ * launches of the plan's solo segment -- so a test reaches the counters' wrap at 2^32 without a
+ * billion launches.  Waits for the plan's stream, then writes the whole state (count = tickets, the
+ * timeout word 0, the solo words as xg_eng_solo_state_after gives them; the step stamps stay) and
+ * sets the host's ticket base, armed-launch base and doorbell epoch to match.  A captured graph's
+ * replay zeroes the state as before, whatever was preset.  XG_EARG for a null plan, a plan with no
+ * engine segment, and a nonzero `armed` on a plan that is not armed or whose segment is not solo. */
+int xg_plan_engine_preset(xg_plan *p, unsigned tickets, unsigned armed);
 /* Mark only the steps whose completion time a Timer reads (need: xg_sched_timed_steps of the
  * plan's schedule; NULL = every step, the default; the last step is always marked).  An unmarked
  * step costs no clock stamp in xg_plan_run and is reported as done when the next marked step is.

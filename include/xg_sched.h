@@ -476,6 +476,57 @@ inline XG_HD xg_small_at xg_small_index(uint32_t b, uint32_t copies, int64_t len
 int xg_small_piece_at(int64_t b, int64_t copies, int64_t len, int64_t piece, int k, int64_t *copy, int64_t *off,
                       int64_t *n);
 
+/* The step engines' launch counters (kernels.h EngineState).  Every counter is
+ * a cumulative 32-bit word in device memory that no launch resets: a launch is told what the
+ * launches before it added (a BASE the host keeps) and compares the word with base + its own share,
+ * by difference or by equality, in uint32_t arithmetic -- which agrees with the word modulo 2^32
+ * whatever the divisor, so nothing here changes when a counter passes 2^31 or 2^32.  The same
+ * functions run in the kernels (every "which value do I wait for / am I the last" decision there is
+ * one of these) and on the host; pieces.c holds their external definitions, and
+ * tests/test_engine_counters.py walks them across the wrap.
+ *
+ * Grid engine (step_engine_kernel), counter `count`: one ticket per workgroup and barrier.  A
+ * launch of W workgroups over n steps takes xg_eng_grid_tickets of them: an armed launch passes one
+ * more barrier, in front of step 0, whose target xg_eng_grid_pre_target is also the base of its
+ * steps; the barrier behind step s opens at xg_eng_grid_target.  A workgroup whose ticket (the
+ * counter after its own increment) is the target arrived last; the others wait while
+ * xg_eng_waiting.  (The counter then reads at most W - 1 past the target: workgroups that went on
+ * to the next barrier.) */
+inline XG_HD uint32_t xg_eng_grid_tickets(uint32_t W, uint32_t nsteps, int armed)
+{
+    return (nsteps + (armed ? 1u : 0u)) * W;
+}
+inline XG_HD uint32_t xg_eng_grid_pre_target(uint32_t base, uint32_t W) { return base + W; }
+inline XG_HD uint32_t xg_eng_grid_target(uint32_t base, uint32_t W, uint32_t s) { return base + (s + 1u) * W; }
+inline XG_HD int xg_eng_waiting(uint32_t count, uint32_t target) { return (int32_t)(count - target) < 0; }
+inline XG_HD int xg_eng_last(uint32_t ticket, uint32_t target) { return ticket == target; }
+/* Solo engine (solo_engine_kernel), ARMED launches of R rails only; base = the armed launches of
+ * the segment since the state was last zeroed.  `arrive` counts resident rails: rail 0 announces
+ * `ready` once the word reaches xg_eng_solo_arrive_target (waiting while xg_eng_waiting).  Finished
+ * rails count on XG_ENG_LINES lines, rail r on line r % L with L = xg_eng_solo_lines(R);
+ * line l holds xg_eng_solo_per_line(R, l) rails.  The rail whose increment of fin[l] gives a has
+ * xg_eng_solo_line_last: it counts on `rails`, and the one whose increment there gives b with
+ * xg_eng_solo_rails_last is the launch's last rail to finish. */
+#define XG_ENG_LINES 16
+inline XG_HD uint32_t xg_eng_solo_lines(uint32_t R) { return R < XG_ENG_LINES ? R : XG_ENG_LINES; }
+inline XG_HD uint32_t xg_eng_solo_per_line(uint32_t R, uint32_t line)
+{
+    return (R - line - 1u) / xg_eng_solo_lines(R) + 1u;
+}
+inline XG_HD uint32_t xg_eng_solo_arrive_target(uint32_t base, uint32_t R) { return (base + 1u) * R; }
+inline XG_HD int xg_eng_solo_line_last(uint32_t a, uint32_t base, uint32_t R, uint32_t line)
+{
+    return a == (base + 1u) * xg_eng_solo_per_line(R, line);
+}
+inline XG_HD int xg_eng_solo_rails_last(uint32_t b, uint32_t base, uint32_t R)
+{
+    return b == (base + 1u) * xg_eng_solo_lines(R);
+}
+/* The solo words as `armed` armed launches of R rails leave them from a zeroed state: go = the
+ * last launch's epoch on every relay line (pieces.c; xg.h xg_plan_engine_preset writes these). */
+typedef struct { uint32_t arrive, rails, go, fin[XG_ENG_LINES]; } xg_eng_solo_state;
+void xg_eng_solo_state_after(uint32_t R, uint32_t armed, xg_eng_solo_state *out);
+
 /* The kernel of one copy launch (pieces.c).  A launch of bytes > 0 runs exactly one KIND, chosen
  * once at plan load from what the launch is (facts) and the context's knobs (rules), by this
  * precedence:

@@ -14,6 +14,7 @@
 #include "xg_sched.h"
 
 #include <stdlib.h>
+#include <string.h>
 
 int64_t xg_piece_size(const int64_t *lens, int n, int64_t chunk, int cus, int64_t wg_cost)
 {
@@ -82,6 +83,32 @@ int xg_small_piece_at(int64_t b, int64_t copies, int64_t len, int64_t piece, int
     if (off) *off = a.off;
     if (n) *n = a.n;
     return 0;
+}
+
+/* ... of the step engines' counter arithmetic */
+extern inline uint32_t xg_eng_grid_tickets(uint32_t W, uint32_t nsteps, int armed);
+extern inline uint32_t xg_eng_grid_pre_target(uint32_t base, uint32_t W);
+extern inline uint32_t xg_eng_grid_target(uint32_t base, uint32_t W, uint32_t s);
+extern inline int xg_eng_waiting(uint32_t count, uint32_t target);
+extern inline int xg_eng_last(uint32_t ticket, uint32_t target);
+extern inline uint32_t xg_eng_solo_lines(uint32_t R);
+extern inline uint32_t xg_eng_solo_per_line(uint32_t R, uint32_t line);
+extern inline uint32_t xg_eng_solo_arrive_target(uint32_t base, uint32_t R);
+extern inline int xg_eng_solo_line_last(uint32_t a, uint32_t base, uint32_t R, uint32_t line);
+extern inline int xg_eng_solo_rails_last(uint32_t b, uint32_t base, uint32_t R);
+
+/* The solo engine's words after `armed` armed launches of R rails (xg_sched.h): every launch adds
+ * R to arrive, a line's rails to its fin word and the lines to rails, all modulo 2^32. */
+void xg_eng_solo_state_after(uint32_t R, uint32_t armed, xg_eng_solo_state *out)
+{
+    uint32_t l;
+    if (!out) return;
+    memset(out, 0, sizeof *out);
+    if (R < 1) return;
+    out->arrive = armed * R;
+    out->rails = armed * xg_eng_solo_lines(R);
+    out->go = armed;
+    for (l = 0; l < xg_eng_solo_lines(R); ++l) out->fin[l] = armed * xg_eng_solo_per_line(R, l);
 }
 
 /* ... and of the strided placement's tile arithmetic */

@@ -41,7 +41,7 @@
 #include <stdint.h>
 #include <type_traits>
 
-#include "../../include/xg_sched.h"     // xg_small_index: the one host / device function of this file
+#include "../../include/xg_sched.h"     // the host / device functions of this file: xg_small_index, xg_vec_piece_at, xg_eng_*
 #include "dcopy.h"                      // kThreads, DCopy, DFix: shared with the host's table builder
 
 namespace xgk {
@@ -425,8 +425,10 @@ __global__ __launch_bounds__(kThreads) void copy_kernel_q(const DCopy *__restric
 //      barrier (release fence by one lane before arriving, acquire fence after
 //      the wait, before any load of step s+1), and no early load.
 // State: a cumulative ticket counter (never reset between launches: each launch
-// gets the tickets taken before it as `base`; the host re-zeroes it only after a
-// timeout) and a timeout word.  Spins are bounded: a timed-out workgroup sets
+// gets the tickets taken before it as `base`; the host re-zeroes it after a
+// timeout and around a graph replay) and a timeout word.  What a workgroup waits
+// for and who arrived last is decided by xg_sched.h's xg_eng_* functions alone,
+// modulo 2^32 (tests/test_engine_counters.py, tests/test_gpu_engine_wrap.py).  Spins are bounded: a timed-out workgroup sets
 // the word and leaves, so a broken residency assumption ends the launch
 // instead of hanging; the host checks the word after the launch (xg_plan_check).
 struct EngineState {
@@ -439,13 +441,13 @@ struct EngineState {
     // relay: rail 0 saw the ring of this epoch -- written to kGoLines separate 128-B lines
     // at once (one store per lane), rail r polls line r % kGoLines, so hundreds of
     // polling rails do not queue on one L2 line
-    unsigned go[16][32];
+    unsigned go[XG_ENG_LINES][32];
     // rails finished, counted on the same 16 lines (rail r on line r % 16); the last of
     // a line counts on `rails`, the last of those rings `done` (two short queues of
     // atomics instead of one of R)
-    unsigned fin[16][32];
+    unsigned fin[XG_ENG_LINES][32];
 };
-constexpr int kGoLines = 16;
+constexpr int kGoLines = XG_ENG_LINES;
 
 
 template <int B>
@@ -510,30 +512,30 @@ __device__ __forceinline__ bool poll_word(g_u32 *w, unsigned v, g_u32 *tmo)
 }
 
 // lane 0 of a finished rail: count it; the launch's last rail tells the host
-__device__ __forceinline__ void rail_finished(EngineState *st, int rail, int R, Doorbell *db, unsigned epoch)
+// (base: the armed launches before this one, xg_sched.h xg_eng_solo_line_last)
+__device__ __forceinline__ void rail_finished(EngineState *st, int rail, int R, unsigned base, Doorbell *db,
+                                              unsigned epoch)
 {
-    const int L = R < kGoLines ? R : kGoLines;
-    const int line = rail % L;
-    const unsigned per_line = (unsigned)((R - line - 1) / L + 1);     // rails on this line
+    const unsigned line = (unsigned)rail % xg_eng_solo_lines((unsigned)R);
     const unsigned a = __hip_atomic_fetch_add((g_u32 *)&st->fin[line][0], 1u, __ATOMIC_RELAXED,
                                               __HIP_MEMORY_SCOPE_AGENT) + 1;
-    if (a % per_line) return;
+    if (!xg_eng_solo_line_last(a, base, (unsigned)R, line)) return;
     const unsigned b = __hip_atomic_fetch_add((g_u32 *)&st->rails, 1u, __ATOMIC_RELAXED,
                                               __HIP_MEMORY_SCOPE_AGENT) + 1;
-    if (b % (unsigned)L == 0) ring_done(db, epoch);
+    if (xg_eng_solo_rails_last(b, base, (unsigned)R)) ring_done(db, epoch);
 }
 
 // B: 16-B loads per lane per unit -> units of B * 4 KiB (the host cuts the step's
 // transfers to that size and picks B so that a step has enough units to spread).
 // db != nullptr: armed launch -- workgroup 0 waits for the ring, then every
-// workgroup passes one extra grid barrier (tickets base .. base + W) before step 0.
+// workgroup passes one extra grid barrier (xg_eng_grid_pre_target) before step 0.
 template <int B>
 __global__ __launch_bounds__(kThreads) void step_engine_kernel(const DCopy *__restrict__ pieces,
                                                                const int *__restrict__ step_begin, int nsteps,
                                                                EngineState *st, unsigned long long *stamps,
                                                                unsigned base, Doorbell *db, unsigned epoch)
 {
-    // compare tickets by difference, which is wrap-safe
+    // targets, waits and last arrivers: xg_sched.h xg_eng_*, modulo 2^32 (tests/test_engine_counters.py)
     const unsigned W = gridDim.x;
     g_u32 *count = (g_u32 *)&st->count;
     g_u32 *tmo = (g_u32 *)&st->tmo;
@@ -544,10 +546,10 @@ __global__ __launch_bounds__(kThreads) void step_engine_kernel(const DCopy *__re
         if (threadIdx.x == 0) {
             bool ok = blockIdx.x != 0 || wait_ring(db, epoch);
             if (!ok) __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            const unsigned target = base + W;
+            const unsigned target = xg_eng_grid_pre_target(base, W);
             __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             for (unsigned spins = 0;
-                 (int)(__hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0;) {
+                 xg_eng_waiting(__hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), target);) {
                 __builtin_amdgcn_s_sleep(1);
                 if (++spins > kRingSpins || __hip_atomic_load(tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
                     __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -561,7 +563,7 @@ __global__ __launch_bounds__(kThreads) void step_engine_kernel(const DCopy *__re
             if (blockIdx.x == 0 && threadIdx.x == 0) ring_done(db, epoch);
             return;
         }
-        base += W;
+        base = xg_eng_grid_pre_target(base, W);     // the steps' tickets follow the pre-barrier's
     }
     // This workgroup's first unit of the next step is LOADED while the barrier is
     // pending (into v[]) and stored once it opens: the load latency of each step
@@ -592,7 +594,7 @@ __global__ __launch_bounds__(kThreads) void step_engine_kernel(const DCopy *__re
         const int fl = flag[s];
         if (fl) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's stores performed
         __syncthreads();
-        const unsigned target = base + (unsigned)(s + 1) * W;
+        const unsigned target = xg_eng_grid_target(base, W, (unsigned)s);
         bool last = false;
         if (threadIdx.x == 0) {
             if (fl == 2) {               // publish: write the XCD's L2 back before arriving
@@ -600,7 +602,7 @@ __global__ __launch_bounds__(kThreads) void step_engine_kernel(const DCopy *__re
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             }
             const unsigned t = __hip_atomic_fetch_add(count, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1;
-            last = t == target;
+            last = xg_eng_last(t, target);
             if (last) {
                 stamps[s] = (unsigned long long)wall_clock64();
                 if (db && s + 1 == nsteps) ring_done(db, epoch);
@@ -616,7 +618,7 @@ __global__ __launch_bounds__(kThreads) void step_engine_kernel(const DCopy *__re
         }
         if (threadIdx.x == 0 && !last) {
             unsigned spins = 0;
-            while ((int)(__hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) < 0) {
+            while (xg_eng_waiting(__hip_atomic_load(count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), target)) {
                 __builtin_amdgcn_s_sleep(1);
                 if (++spins > (1u << 22) || __hip_atomic_load(tmo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
                     __hip_atomic_store(tmo, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -827,8 +829,9 @@ __global__ __launch_bounds__(WV * 64) void solo_engine_kernel(const unsigned lon
                                                                    uint8_t *dst_base, const int *__restrict__ meta,
                                                                    int nsteps, EngineState *st,
                                                                    unsigned long long *stamps, int stride,
-                                                                   Doorbell *db, unsigned epoch)
+                                                                   Doorbell *db, unsigned epoch, unsigned base)
 {
+    // base (armed launches only): the armed launches of this segment since the state was zeroed
     const int wave = (int)threadIdx.x >> 6, lane = (int)threadIdx.x & 63;
     const int rail = (int)blockIdx.x, R = (int)gridDim.x;
     __shared__ unsigned long long ldesc[kSoloMaxPieces];
@@ -857,12 +860,11 @@ __global__ __launch_bounds__(WV * 64) void solo_engine_kernel(const unsigned lon
         bool ok = true, relay_go = false;
         if (db) {
             g_u32 *tmo = (g_u32 *)&st->tmo;
-            const unsigned old = __hip_atomic_fetch_add((g_u32 *)&st->arrive, 1u, __ATOMIC_RELAXED,
-                                                        __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_fetch_add((g_u32 *)&st->arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (rail == 0) {
-                const unsigned all = (old / (unsigned)R + 1) * (unsigned)R;
-                for (unsigned spins = 0; ok && (int)(__hip_atomic_load((g_u32 *)&st->arrive, __ATOMIC_RELAXED,
-                                                                       __HIP_MEMORY_SCOPE_AGENT) - all) < 0; ++spins) {
+                const unsigned all = xg_eng_solo_arrive_target(base, (unsigned)R);
+                for (unsigned spins = 0; ok && xg_eng_waiting(__hip_atomic_load((g_u32 *)&st->arrive, __ATOMIC_RELAXED,
+                                                                                __HIP_MEMORY_SCOPE_AGENT), all); ++spins) {
                     __builtin_amdgcn_s_sleep(1);
                     ok = spins < kRingSpins;
                 }
@@ -881,7 +883,7 @@ __global__ __launch_bounds__(WV * 64) void solo_engine_kernel(const unsigned lon
     if (relay_now && threadIdx.x < kGoLines)   // one store per lane: every relay line at once
         __hip_atomic_store((g_u32 *)&st->go[threadIdx.x][0], epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (give_up) {
-        if (threadIdx.x == 0) rail_finished(st, rail, R, db, epoch);   // still counted
+        if (threadIdx.x == 0) rail_finished(st, rail, R, base, db, epoch);   // still counted
         return;
     }
     const uint64_t l16 = (uint64_t)lane;
@@ -906,7 +908,7 @@ __global__ __launch_bounds__(WV * 64) void solo_engine_kernel(const unsigned lon
     if (threadIdx.x == 0) {
         t_end = (unsigned long long)wall_clock64();
         s_end = k > 0 ? lcstep[k - 1] + 1 : 0;
-        if (db) rail_finished(st, rail, R, db, epoch);      // the last rail to finish tells the host
+        if (db) rail_finished(st, rail, R, base, db, epoch);      // the last rail to finish tells the host
     }
     __syncthreads();
     for (int i = (int)threadIdx.x; i < nsteps; i += kT) stamps[(size_t)rail * stride + i] = i >= s_end ? t_end : ts[i];

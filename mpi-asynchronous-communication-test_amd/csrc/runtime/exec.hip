@@ -217,14 +217,16 @@ int launch_seg(xg_plan *p, const EngSeg &g, hipStream_t stream, bool armed)
     int rc;
     if (p->engine_reset) {
         HIPCHK(hipMemsetAsync(p->d_engine, 0, sizeof(xgk::EngineState), stream));
-        p->engine_base = 0;
+        p->engine_base = p->solo_base = 0;
         p->engine_reset = false;
     }
     const int n = g.s1 - g.s0;
     xgk::Doorbell *db = armed ? p->db : nullptr;
     const unsigned epoch = armed ? ++p->epoch : 0;
-    const unsigned base = p->engine_base;
-    if (!g.solo) p->engine_base += (unsigned)(n + (armed ? 1 : 0)) * (unsigned)g.w;
+    // what the launches before this one added to the state's counters (xg_sched.h xg_eng_*)
+    const unsigned base = g.solo ? p->solo_base : p->engine_base;
+    if (!g.solo) p->engine_base += xg_eng_grid_tickets((unsigned)g.w, (unsigned)n, db != nullptr);
+    else if (db) ++p->solo_base;
     bool kt;
     if ((rc = kt_before(c, stream, &kt))) return rc;
     unsigned long long *stamps = reinterpret_cast<unsigned long long *>(p->d_engine + 1) + g.s0;
@@ -237,7 +239,7 @@ int launch_seg(xg_plan *p, const EngSeg &g, hipStream_t stream, bool armed)
                        : g.gran == 4  ? xgk::solo_engine_kernel<xgk::kSoloK, 1, 4>
                                       : xgk::solo_engine_kernel<xgk::kSoloK / 2, 1, 1>;
         hipLaunchKernelGGL(k, dim3(g.w), dim3(g.wv != 1 ? xgk::kSoloThreads : 64), 0, stream, p->d_solo + g.u0,
-                           g.npieces, g.sbase, g.dbase, sb, n, p->d_engine, stamps, p->nsteps, db, epoch);
+                           g.npieces, g.sbase, g.dbase, sb, n, p->d_engine, stamps, p->nsteps, db, epoch, base);
     } else {
         const auto k = g.b == 1   ? xgk::step_engine_kernel<1>
                        : g.b == 4 ? xgk::step_engine_kernel<4>
@@ -509,6 +511,42 @@ extern "C" int xg_plan_set_local_only(xg_plan *p, int on)
     for (const StepR &st : p->steps)
         if (on && st.self_local) return XG_EARG;
     p->local_only = on != 0;
+    return XG_OK;
+}
+
+// Test hook: the engine state of p as earlier launches would have left it -- `tickets` grid tickets
+// taken in all, `armed` armed launches of the plan's (solo) segment -- so a test starts a plan's
+// cumulative counters next to 2^31 or 2^32 instead of launching it a billion times.  The whole
+// state is written (stamps untouched) and the host's bases and epoch follow; the doorbell's words
+// hold the last epoch, as an armed run leaves them.
+extern "C" int xg_plan_engine_preset(xg_plan *p, unsigned tickets, unsigned armed)
+{
+    if (!p || p->segs.empty()) return XG_EARG;
+    const EngSeg &g = p->segs[0];
+    if (armed && (!p->db || !g.solo)) return XG_EARG;
+    HIPCHK(hipSetDevice(p->ctx->device));
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));
+    xg_eng_solo_state ss;
+    xg_eng_solo_state_after(g.solo ? (uint32_t)g.w : 0u, armed, &ss);
+    xgk::EngineState es;
+    memset(&es, 0, sizeof es);
+    es.count = tickets;
+    es.arrive = ss.arrive;
+    es.rails = ss.rails;
+    for (int l = 0; l < xgk::kGoLines; ++l) {
+        es.go[l][0] = ss.go;
+        es.fin[l][0] = ss.fin[l];
+    }
+    HIPCHK(hipMemcpy(p->d_engine, &es, sizeof es, hipMemcpyHostToDevice));
+    p->engine_base = tickets;
+    p->solo_base = armed;
+    p->epoch = armed;
+    p->engine_reset = false;
+    if (p->db) {
+        __atomic_store_n(&p->db->ring, armed, __ATOMIC_RELEASE);
+        __atomic_store_n(&p->db->ready, armed, __ATOMIC_RELEASE);
+        __atomic_store_n(&p->db->done, armed, __ATOMIC_RELEASE);
+    }
     return XG_OK;
 }
 

@@ -155,6 +155,8 @@ struct xg_plan : PlanTables {
     xgk::EngineState *d_engine = nullptr;   // state (16 B, zeroed at load) followed by stamps: rail r's of step
                                             // s at [r * nsteps + s] (grid segments: rail 0)
     unsigned engine_base = 0;               // barrier tickets taken by earlier launches (wraps)
+    unsigned solo_base = 0;                 // armed solo launches since the state was last zeroed (wraps; not
+                                            // `epoch`, which outlives an engine_reset)
     bool engine_reset = false;              // zero the state before the next launch
     xgk::Doorbell *db = nullptr;            // host-pinned doorbell of armed runs (may_arm), or null
     unsigned long long *d_solo = nullptr;   // solo_desc

@@ -78,6 +78,14 @@ class SoloShape(C.Structure):
     _fields_ = [("rails", C.c_int32), ("npieces", C.c_int32), ("nrows", C.c_int32), ("nmeta", C.c_int32)]
 
 
+ENG_LINES = 16                          # XG_ENG_LINES
+
+
+class EngSoloState(C.Structure):
+    """xg_eng_solo_state: the solo engine's counter words after some armed launches"""
+    _fields_ = [("arrive", C.c_uint32), ("rails", C.c_uint32), ("go", C.c_uint32), ("fin", C.c_uint32 * ENG_LINES)]
+
+
 class Span(C.Structure):
     _fields_ = [("src", C.c_uint64), ("dst", C.c_uint64), ("len", C.c_uint64)]
 
@@ -502,6 +510,19 @@ def host():
         h.xg_piece_size.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_int, C.c_int64]
         h.xg_extent_tiles.argtypes = [C.POINTER(C.c_int64), C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int32)]
         h.xg_small_piece_at.argtypes = [C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int] + [C.POINTER(C.c_int64)] * 3
+        # the step engines' counter arithmetic (xg_sched.h xg_eng_*): uint32 in, uint32 or a truth value out
+        u32 = C.c_uint32
+        for fn, nargs, res in (("xg_eng_grid_pre_target", 2, u32), ("xg_eng_grid_target", 3, u32),
+                               ("xg_eng_waiting", 2, C.c_int), ("xg_eng_last", 2, C.c_int),
+                               ("xg_eng_solo_lines", 1, u32), ("xg_eng_solo_per_line", 2, u32),
+                               ("xg_eng_solo_arrive_target", 2, u32), ("xg_eng_solo_line_last", 4, C.c_int),
+                               ("xg_eng_solo_rails_last", 3, C.c_int)):
+            getattr(h, fn).argtypes = [u32] * nargs
+            getattr(h, fn).restype = res
+        h.xg_eng_grid_tickets.argtypes = [u32, u32, C.c_int]
+        h.xg_eng_grid_tickets.restype = u32
+        h.xg_eng_solo_state_after.argtypes = [u32, u32, C.POINTER(EngSoloState)]
+        h.xg_eng_solo_state_after.restype = None
         h.xg_launch_facts_add.restype = None
         h.xg_launch_facts_add.argtypes = [C.POINTER(LaunchFacts), C.POINTER(Copy)]
         h.xg_copy_launch_choose.argtypes = [C.POINTER(LaunchFacts), C.POINTER(CopyRules), C.POINTER(CopyChoice)]
@@ -1176,6 +1197,7 @@ def device():
         d.xg_vplans_run.argtypes = [C.POINTER(vp), ip, C.POINTER(C.c_double)]
         d.xg_vplans_run_rccl.argtypes = [C.POINTER(vp), ip, C.POINTER(C.c_double)]
         d.xg_plan_set_local_only.argtypes = [vp, ip]
+        d.xg_plan_engine_preset.argtypes = [vp, C.c_uint, C.c_uint]
         d.xg_plan_set_step_marks.argtypes = [vp, C.POINTER(C.c_uint8)]
         d.xg_self_max.restype = i64
         d.xg_self_max.argtypes = [vp]
@@ -1821,6 +1843,11 @@ class MethodRun:
         """test hook (virtual GPU): run this GPU's share alone -- copy launches only, its RCCL
         calls and in-loop barriers left out (xg_plan_set_local_only)"""
         _check(_dev.xg_plan_set_local_only(self._p, 1 if on else 0), "xg_plan_set_local_only")
+
+    def engine_preset(self, tickets=0, armed=0):
+        """test hook: the engine counters as earlier launches would have left them -- `tickets`
+        grid tickets, `armed` armed solo launches (xg_plan_engine_preset)"""
+        _check(_dev.xg_plan_engine_preset(self._p, tickets & 0xFFFFFFFF, armed & 0xFFFFFFFF), "xg_plan_engine_preset")
 
     def verify(self):
         ns = max(1, self.nslots)
