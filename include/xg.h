@@ -370,13 +370,22 @@ int xg_exchange_w(xg_ctx *ctx, int method, int procs, int cb_nodes, const xg_ext
  * end mark on the context's stream, waits, and returns the device seconds between the marks
  * (device_seconds may be NULL); non-temporal by the context's copy variant, by size as a placement
  * plan's launch when that is 0.  xg_vecplace_tiles / _dispatches: the launch's workgroups and kernel
- * dispatches (0 for an empty list). */
+ * dispatches (0 for an empty list).
+ * xg_vecplace_load_views: the same list as ONE launch of copy_kernel_vv, a workgroup per tile of one
+ * VIEW -- the rows xg_vrow_views (xg_sched.h) recognises as one striped file view, the tile dealt
+ * across them (xg_view_piece_at), so that a tile touches k x len contiguous bytes per block index on
+ * the striped side.  Its tables are xg_view_tables_build's with the same three settings; it decides
+ * nothing on the device side either, places the same bytes, and its object is run, asked and freed by
+ * the same functions.  xg_vecplace_views: its views of more than one row (0 for an object of
+ * xg_vecplace_load). */
 typedef struct xg_vecplace xg_vecplace;
 int xg_vecplace_load(xg_ctx *ctx, xg_regions *r, const xg_vrow *rows, int64_t n, xg_vecplace **out);
+int xg_vecplace_load_views(xg_ctx *ctx, xg_regions *r, const xg_vrow *rows, int64_t n, xg_vecplace **out);
 int xg_vecplace_run(xg_vecplace *v, double *device_seconds);
 int xg_vecplace_free(xg_vecplace *v);
 int64_t xg_vecplace_tiles(const xg_vecplace *v);
 int xg_vecplace_dispatches(const xg_vecplace *v);
+int64_t xg_vecplace_views(const xg_vecplace *v);
 
 /* xg_exchange_w with the placement described by STRIDED RUNS (exchange_w.c too; the list rules,
  * xg_vecs_check and xg_vecs_expand: xg_sched.h): what xg_exchange_w does for xg_vecs_expand of the
@@ -391,12 +400,16 @@ int xg_vecplace_dispatches(const xg_vecplace *v);
  * extents), or any list with XG_VEC_COPY=0, is placed as before -- xg_vecs_expand into
  * xg_exchange_w; the ranks settle this together (one MAX all-reduce), so that all of them take the
  * same road.  xg_exchange_wv_tiles: the copy_kernel_v workgroups of this process's last
- * xg_exchange_wv placement (0 when it went by the expansion). */
+ * xg_exchange_wv placement (0 when it went by the expansion).  With XG_VEC_VIEWS=1 in the environment
+ * the rows are loaded by xg_vecplace_load_views (the placement posts no RCCL call, so a rank may set
+ * it alone; the routing above is untouched); xg_exchange_wv_views: that placement's
+ * xg_vecplace_views, 0 otherwise. */
 int xg_exchange_wv(xg_ctx *ctx, int method, int procs, int cb_nodes, const xg_vec *v, int64_t n,
                    const int64_t *dom_bytes, const int *rank_list, int comm_size, void *send, void *recv,
                    xg_timer *timers, int iter, int ntimes, const xg_run_opts *opts,
                    int64_t *bad_slots, int64_t *bad_vecs, double *place_s, char *err, size_t errlen);
 int64_t xg_exchange_wv_tiles(void);
+int64_t xg_exchange_wv_views(void);
 
 /* The operators under the reference's names (mpi_test.c line of the original). */
 #define XG_METHOD_DECL(name)                                                                     \

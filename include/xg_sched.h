@@ -724,6 +724,82 @@ int xg_vec_piece(const xg_vrow *row, int64_t tile_bytes, int tile_pieces, int64_
  * when it passes INT32_MAX (a launch's workgroups are counted in 32 bits) or an argument is bad. */
 int64_t xg_vec_rows_tiles(const xg_vrow *rows, int64_t n, int64_t tile_bytes, int tile_pieces, int32_t *tile0);
 
+/* ---------------------------------------------------------------- views (vecs.c)
+ * A VIEW is a set of k >= 1 rows of one GPU's xg_vrow list that are one striped file view: the same
+ * src_buf and dst_buf, the same len, count, src_step and dst_step, len <= tile_bytes, and offsets on
+ * one side -- the STRIPED side -- exactly len apart from row to row (the other, dense, side may sit
+ * anywhere).  A tile dealt across the rows of a view (xg_view_piece_at) writes (dst-striped, the a2m
+ * scatter) or reads (src-striped, the m2a gather) k x len contiguous bytes per block index where a
+ * tile of one row touches len.
+ * xg_vrow_views finds them, O(n log n) time and O(n) memory: the row indices sorted by (bufs, len,
+ * count, steps, destination offset, source offset, list index) are chained where the destination
+ * offsets are len apart; the rows that chained with nothing are sorted once more with the source
+ * offset ahead of the destination's and chained by it (a chain that qualifies both ways is
+ * dst-striped).  The rows of a view need not be neighbours in the list.  A chain longer than
+ * kmax = min(tile_pieces, max(1, tile_bytes / len)) is cut into consecutive views of kmax rows, the
+ * last one shorter; a row that chains with nothing, one with len > tile_bytes and one with len <= 0
+ * or count <= 0 is a view of k = 1.  Views come in the order of their first rows in the first sort,
+ * so two lists that are permutations of each other give the same views.
+ * order: n row indices, the views' rows one view behind the other, each in ascending striped offset;
+ * view_k: rows per view; view_kind: XG_VIEW_* per view (either may be NULL).  Returns the view count,
+ * -1 for bad arguments or no memory. */
+enum { XG_VIEW_SINGLE = 0, XG_VIEW_DST_STRIPED = 1, XG_VIEW_SRC_STRIPED = 2 };
+int64_t xg_vrow_views(const xg_vrow *rows, int64_t n, int64_t tile_bytes, int tile_pieces, int64_t *order,
+                      int32_t *view_k, int32_t *view_kind);
+/* Tile arithmetic of a view of k rows, host and device code alike (pieces.c holds the external
+ * definitions).  len <= tile_bytes: jb = clamp(tile_bytes / (k x len), 1, tile_pieces / k) blocks per
+ * row go to a tile, ceil(count / jb) tiles; lane q of tile t takes row i = q % k (the fastest index:
+ * a tile's pieces ascend on the striped side) and block j = t x jb + q / k, and is live when
+ * q < k x jb and j < count.  With k = 1 this is xg_vec_piece_at's deal exactly.  len > tile_bytes
+ * (k = 1): that function's long-block deal, lane 0 takes piece t.  64-bit throughout but for the
+ * division by k; xg_view_tiles is INT64_MAX when it does not fit, 0 for a bad argument. */
+inline XG_HD int64_t xg_view_jb(int64_t len, int k, int64_t tile_bytes, int tile_pieces)
+{
+    const int64_t b = tile_bytes / ((int64_t)k * len), hi = tile_pieces / k;
+    return b > hi ? (hi < 1 ? 1 : hi) : b < 1 ? 1 : b;
+}
+inline XG_HD int64_t xg_view_tiles(int64_t len, int64_t count, int k, int64_t tile_bytes, int tile_pieces)
+{
+    if (len <= 0 || count <= 0 || k < 1 || tile_bytes < 1 || tile_pieces < 1) return 0;
+    if (len <= tile_bytes) {
+        const int64_t jb = xg_view_jb(len, k, tile_bytes, tile_pieces);
+        return count / jb + (count % jb != 0);
+    }
+    return xg_vec_row_tiles(len, count, tile_bytes, tile_pieces);
+}
+/* Lane q of tile t of a view whose rows have blocks of len bytes, count of them, and go jb to a
+ * tile: n bytes (0: the lane is idle) at byte `off` of block `block` of the view's row `row`, that is
+ * at the row's own offsets + block x step + off on either side. */
+typedef struct { int32_t row, pad; int64_t block, off, n; } xg_view_at;
+inline XG_HD xg_view_at xg_view_piece_at(int64_t len, int64_t count, int k, int64_t jb, int64_t tile_bytes, int64_t t,
+                                         int q)
+{
+    xg_view_at p;
+    p.row = p.pad = 0;
+    p.block = p.off = p.n = 0;
+    if (len <= tile_bytes) {
+        const uint32_t uq = (uint32_t)q, uk = (uint32_t)k, b = uq / uk;       /* 32-bit: k is uniform */
+        const int64_t j = t * jb + b;
+        if ((int64_t)b < jb && j < count) {
+            p.row = (int32_t)(uq - b * uk);
+            p.block = j;
+            p.n = len;
+        }
+    } else if (q == 0) {
+        const int64_t ppb = len / tile_bytes + (len % tile_bytes != 0);
+        p.block = t / ppb;
+        p.off = (t - p.block * ppb) * tile_bytes;
+        p.n = len - p.off < tile_bytes ? len - p.off : tile_bytes;
+    }
+    return p;
+}
+/* xg_view_piece_at over the k rows of a view (rows[0 .. k), in view order), range-checked: 0 and
+ * *row, the offsets and *n of lane q of tile t, or -1 when the rows are no view of k (len, count or a
+ * step differs, k does not fit a tile), t is no tile of it, q no lane of a tile or an argument is out
+ * of range (pieces.c). */
+int xg_view_piece(const xg_vrow *rows, int k, int64_t tile_bytes, int tile_pieces, int64_t t, int q, int *row,
+                  int64_t *src_off, int64_t *dst_off, int64_t *n);
+
 /* fill: `nsegs` consecutive d-byte segments at `off` in the SEND region,
  * segment i = fingerprint(rank, seed0 + i, iter) (prepare_*_data loops). */
 typedef struct { int32_t rank, seed0; int64_t off; int32_t nsegs, pad; } xg_segrun;
@@ -855,6 +931,34 @@ int64_t xg_vec_tables_dispatch_bytes(const xg_vec_tables *t, int k);    /* k in 
  * launch_max ..", then "row i src dst src_step dst_step len count", "tile0 i v", "cut i v",
  * "dbytes i v".  Returns the length (without the final NUL); at most cap bytes are written. */
 int64_t xg_vec_tables_dump(const xg_vec_tables *t, char *buf, int64_t cap);
+
+/* ---------------------------------------------------------------- view launch tables (vec_tables.cc)
+ * What xg_vecplace_load_views (xg.h) makes of the same list: everything one copy_kernel_vv launch
+ * reads, one workgroup per tile of one VIEW (xg_vrow_views, xg_view_piece_at).
+ *   device rows  as above, permuted into view order (xg_vrow_views' order);
+ *   views        {first device row, k, jb} per view;
+ *   tile0        views + 1 entries, the prefix of xg_view_tiles;
+ *   cuts         by the row tables' rule, word for word, over the views' tiles (a view's tile bytes
+ *                are those of a row of blocks of k x len bytes, jb to a tile).  O(views + cuts) time.
+ * The refusals are xg_vec_tables_build's (the row named is the list's), with more than INT32_MAX
+ * tiles counted over the views.  n == 0 is XG_OK. */
+typedef struct xg_view_tables xg_view_tables;
+int xg_view_tables_build(const xg_vrow *rows, int64_t n, const uint64_t base[XG_NBUF], const int64_t bytes[XG_NBUF],
+                         int64_t tile_bytes, int tile_pieces, int64_t launch_max, xg_view_tables **out);
+void xg_view_tables_free(xg_view_tables *t);
+int64_t xg_view_tables_rows(const xg_view_tables *t);
+int64_t xg_view_tables_views(const xg_view_tables *t);                   /* all views */
+int64_t xg_view_tables_multi(const xg_view_tables *t);                   /* ... those of k > 1 */
+int64_t xg_view_tables_tiles(const xg_view_tables *t);
+int xg_view_tables_dispatches(const xg_view_tables *t);
+int64_t xg_view_tables_bytes(const xg_view_tables *t);
+int64_t xg_view_tables_cut(const xg_view_tables *t, int k);              /* k in 0 .. dispatches; -1 outside */
+int64_t xg_view_tables_dispatch_bytes(const xg_view_tables *t, int k);   /* k in 0 .. dispatches - 1; -1 outside */
+int64_t xg_view_tables_order(const xg_view_tables *t, int64_t i);        /* the list index of device row i; -1 outside */
+/* "views rows .. views .. multi .. tiles .. dispatches .. bytes .. tile_bytes .. tile_pieces ..
+ * launch_max ..", then "row i src dst src_step dst_step len count" (device order), "order i list_index",
+ * "view i row0 k jb kind", "tile0 i v", "cut i v", "dbytes i v", as xg_vec_tables_dump. */
+int64_t xg_view_tables_dump(const xg_view_tables *t, char *buf, int64_t cap);
 
 #ifdef __cplusplus
 }

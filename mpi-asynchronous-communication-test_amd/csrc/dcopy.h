@@ -23,6 +23,13 @@ struct DVRow {
     int64_t len, count;
 };
 
+// One view of a strided placement (copy_kernel_vv; built by host/vec_tables.cc from xg_vrow_views):
+// device rows [row0, row0 + k), equal in len, count and steps, their offsets len apart on one side;
+// a tile takes jb blocks of each of them (xg_view_piece_at).
+struct DView {
+    int32_t row0, k, jb, pad;
+};
+
 // Piece table fix-up after the scan: piece k of a packed copy c moves
 // [o, o + len) of it; its staging side (dst of a pack, src of an unpack) is
 // staging base + disp[c] + o.

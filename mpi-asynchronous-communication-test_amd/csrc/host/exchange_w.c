@@ -6,7 +6,8 @@
  * write) or gathers it out of the domain buffer before the exchange (m2a, the collective read).
  *   xg_exchange_w   the placement is a plan (xg_place_plan_build: one copy per extent, run on
  *                   copy_kernel_x where its runs are short);
- *   xg_exchange_wv  the placement is ONE launch of copy_kernel_v over this GPU's rows
+ *   xg_exchange_wv  the placement is ONE launch of copy_kernel_v over this GPU's rows (of
+ *                   copy_kernel_vv over their views with XG_VEC_VIEWS=1)
  *                   (xg_vec_rows_build, xg_vecplace_load): no extent list, no plan, no descriptor per
  *                   block is ever built.  A list of few, long blocks (mean above kVecLenMax) goes
  *                   through xg_vecs_expand into xg_exchange_w, as every list did before.
@@ -245,9 +246,10 @@ static const int64_t kVecLenMax = 1024;
 /* spans per xg_chk_spans launch of the placement check */
 #define VEC_CHK_BATCH 65536
 
-static int64_t g_last_tiles = 0;
+static int64_t g_last_tiles = 0, g_last_views = 0;
 
 int64_t xg_exchange_wv_tiles(void) { return g_last_tiles; }
+int64_t xg_exchange_wv_views(void) { return g_last_views; }
 
 /* every rank passed the same list and domain lengths (every vec field by field: a hash must not
  * depend on the struct's padding) */
@@ -361,8 +363,8 @@ int xg_exchange_wv(xg_ctx *ctx, int method, int procs, int cb_nodes, const xg_ve
     int64_t *lens = NULL, k, region_bytes[XG_NBUF];
     int64_t len_max = kVecLenMax;
     const char *env;
-    int rc, expand = 0;
-    g_last_tiles = 0;
+    int rc, expand = 0, views = 0;
+    g_last_tiles = g_last_views = 0;
     if ((rc = front(&p))) return rc;
     err = p.err; errlen = p.errlen; opts = p.opts;
     if (p.G > 1 && (rc = vecs_agree(ctx, procs, cb_nodes, v, n, dom_bytes, err, errlen))) return rc;
@@ -405,10 +407,17 @@ int xg_exchange_wv(xg_ctx *ctx, int method, int procs, int cb_nodes, const xg_ve
         return by_expansion(&p, v, n, dom_bytes);
     }
     if (rc == XG_OK) rc = adopt(&p, region_bytes, &w.reg);
-    if (rc == XG_OK && (rc = xg_vecplace_load(ctx, w.reg, w.rows, w.nrows, &w.vp)))
+    /* XG_VEC_VIEWS=1: a tile per view (copy_kernel_vv).  The placement posts no RCCL call, so this
+     * rank decides alone.  Off by default; it moves only by profiles/vec_views_ab.py's table */
+    if ((env = getenv("XG_VEC_VIEWS")) && atoi(env) != 0) views = 1;
+    if (rc == XG_OK && (rc = views ? xg_vecplace_load_views(ctx, w.reg, w.rows, w.nrows, &w.vp)
+                                   : xg_vecplace_load(ctx, w.reg, w.rows, w.nrows, &w.vp)))
         snprintf(err, errlen, "placement rows: not loaded (%d, see stderr)", rc);
     if (p.G > 1) rc = agree_peers(ctx, rc, NULL, WHAT, err, errlen);    /* before the exchange's first call */
-    if (rc == XG_OK) g_last_tiles = xg_vecplace_tiles(w.vp);
+    if (rc == XG_OK) {
+        g_last_tiles = xg_vecplace_tiles(w.vp);
+        g_last_views = xg_vecplace_views(w.vp);
+    }
     rc = back(&p, rc, w.reg, lens, vec_run, chk_rows, &w, "vecs");
     free(w.rows); free(lens);
     if (w.vp) xg_vecplace_free(w.vp);

@@ -149,6 +149,36 @@ int64_t xg_vec_rows_tiles(const xg_vrow *rows, int64_t n, int64_t tile_bytes, in
     return tot;
 }
 
+/* ... and of a view's */
+extern inline int64_t xg_view_jb(int64_t len, int k, int64_t tile_bytes, int tile_pieces);
+extern inline int64_t xg_view_tiles(int64_t len, int64_t count, int k, int64_t tile_bytes, int tile_pieces);
+extern inline xg_view_at xg_view_piece_at(int64_t len, int64_t count, int k, int64_t jb, int64_t tile_bytes, int64_t t,
+                                          int q);
+
+/* Lane q of tile t of the view rows[0 .. k) (xg_view_piece_at, xg_sched.h), range-checked. */
+int xg_view_piece(const xg_vrow *rows, int k, int64_t tile_bytes, int tile_pieces, int64_t t, int q, int *row,
+                  int64_t *src_off, int64_t *dst_off, int64_t *n)
+{
+    xg_view_at p;
+    const xg_vrow *r;
+    int i;
+    if (!rows || k < 1 || tile_bytes < 1 || tile_pieces < 1 || k > tile_pieces || t < 0 || q < 0 || q >= tile_pieces ||
+        rows->len <= 0 || rows->count <= 0 || (k > 1 && rows->len > tile_bytes / k))
+        return -1;
+    for (i = 1; i < k; ++i)
+        if (rows[i].len != rows->len || rows[i].count != rows->count || rows[i].src_step != rows->src_step ||
+            rows[i].dst_step != rows->dst_step)
+            return -1;
+    if (t >= xg_view_tiles(rows->len, rows->count, k, tile_bytes, tile_pieces)) return -1;
+    p = xg_view_piece_at(rows->len, rows->count, k, xg_view_jb(rows->len, k, tile_bytes, tile_pieces), tile_bytes, t, q);
+    r = &rows[p.row];
+    if (row) *row = p.row;
+    if (src_off) *src_off = p.n ? r->src_off + p.block * (r->count > 1 ? r->src_step : 0) + p.off : 0;
+    if (dst_off) *dst_off = p.n ? r->dst_off + p.block * (r->count > 1 ? r->dst_step : 0) + p.off : 0;
+    if (n) *n = p.n;
+    return 0;
+}
+
 void xg_launch_facts_add(xg_launch_facts *f, const xg_copy *c)
 {
     if (c->len <= 0) return;

@@ -325,3 +325,132 @@ int64_t xg_vec_rows_build(const xg_sched *s, int ngpus, int g, const xg_vec *v, 
     free(done); free(dense); free(dom);
     return k;
 }
+
+/* ------------------------------------------------------------------ views
+ * Which rows of a GPU's row list are one striped file view (xg_vrow_views, xg_sched.h): the
+ * recognition copy_kernel_vv's tables (vec_tables.cc, xg_view_tables_build) are built from.  The most
+ * common MPI-IO view is a domain striped over the ranks in runs of L bytes: rank r's row holds block
+ * j at r x L + j x P x L of the domain, so the rows of the P ranks are L apart on the domain side and
+ * equal in everything else.  A rank-major vec list puts them cb_nodes apart in the row list, so they
+ * are found by sorting, never by looking at neighbours. */
+typedef struct { const xg_vrow *r; int64_t idx; } vent;
+
+static int cmp64(int64_t a, int64_t b) { return a < b ? -1 : a > b; }
+
+/* everything the rows of a view share; 0 when equal */
+static int cmp_shape(const xg_vrow *a, const xg_vrow *b)
+{
+    int c;
+    if ((c = cmp64(a->src_buf, b->src_buf)) || (c = cmp64(a->dst_buf, b->dst_buf)) || (c = cmp64(a->len, b->len)) ||
+        (c = cmp64(a->count, b->count)) || (c = cmp64(a->src_step, b->src_step)))
+        return c;
+    return cmp64(a->dst_step, b->dst_step);
+}
+
+/* total orders: the shape, the striped offset, the other offset, the list index */
+static int cmp_dst(const void *x, const void *y)
+{
+    const vent *a = (const vent *)x, *b = (const vent *)y;
+    int c;
+    if ((c = cmp_shape(a->r, b->r)) || (c = cmp64(a->r->dst_off, b->r->dst_off)) ||
+        (c = cmp64(a->r->src_off, b->r->src_off)))
+        return c;
+    return cmp64(a->idx, b->idx);
+}
+
+static int cmp_src(const void *x, const void *y)
+{
+    const vent *a = (const vent *)x, *b = (const vent *)y;
+    int c;
+    if ((c = cmp_shape(a->r, b->r)) || (c = cmp64(a->r->src_off, b->r->src_off)) ||
+        (c = cmp64(a->r->dst_off, b->r->dst_off)))
+        return c;
+    return cmp64(a->idx, b->idx);
+}
+
+/* may this row be one of several of a view */
+static int chains(const xg_vrow *r, int64_t tile_bytes) { return r->len > 0 && r->count > 0 && r->len <= tile_bytes; }
+
+/* b follows a in a chain: the same shape, the striped offset len on (an offset that wraps never chains) */
+static int follows(const xg_vrow *a, const xg_vrow *b, int src_side)
+{
+    const int64_t ao = src_side ? a->src_off : a->dst_off, bo = src_side ? b->src_off : b->dst_off;
+    return cmp_shape(a, b) == 0 && ao <= INT64_MAX - a->len && bo == ao + a->len;
+}
+
+/* One view per entry of `first`: its chain's start in the sorted array it was found in.  Views of the
+ * second pass are merged into the first pass's order by their first row's position there (pos1). */
+typedef struct { int64_t pos1, idx; int64_t at, k; int32_t kind; } view;
+
+static int cmp_view(const void *x, const void *y)
+{
+    const view *a = (const view *)x, *b = (const view *)y;
+    int c = cmp64(a->pos1, b->pos1);
+    return c ? c : cmp64(a->idx, b->idx);
+}
+
+int64_t xg_vrow_views(const xg_vrow *rows, int64_t n, int64_t tile_bytes, int tile_pieces, int64_t *order,
+                      int32_t *view_k, int32_t *view_kind)
+{
+    vent *a = NULL, *b = NULL;          /* the first sort; the rows it left single, sorted again */
+    int64_t *pos1 = NULL;               /* a row's position in the first sort */
+    view *v = NULL;
+    int64_t i, e, m = 0, nv = 0, out = 0;
+    if (n < 0 || (n && !rows) || tile_bytes < 1 || tile_pieces < 1) return -1;
+    if (n == 0) return 0;
+    a = (vent *)malloc(sizeof *a * (size_t)n);
+    b = (vent *)malloc(sizeof *b * (size_t)n);
+    pos1 = (int64_t *)malloc(sizeof *pos1 * (size_t)n);
+    v = (view *)malloc(sizeof *v * (size_t)n);
+    if (!a || !b || !pos1 || !v) {
+        free(a); free(b); free(pos1); free(v);
+        return -1;
+    }
+    for (i = 0; i < n; ++i) { a[i].r = &rows[i]; a[i].idx = i; }
+    qsort(a, (size_t)n, sizeof *a, cmp_dst);
+    for (i = 0; i < n; ++i) pos1[a[i].idx] = i;
+    /* pass 1: chains by destination offset; [i, e) is one */
+    for (i = 0; i < n; i = e) {
+        e = i + 1;
+        if (chains(a[i].r, tile_bytes))
+            while (e < n && follows(a[e - 1].r, a[e].r, 0)) ++e;
+        if (e - i == 1) {
+            b[m++] = a[i];
+            continue;
+        }
+        v[nv].pos1 = i; v[nv].idx = a[i].idx; v[nv].at = i; v[nv].k = e - i; v[nv].kind = XG_VIEW_DST_STRIPED;
+        ++nv;
+    }
+    /* pass 2: what is left, by source offset; at < 0 marks a view whose rows are b's */
+    qsort(b, (size_t)m, sizeof *b, cmp_src);
+    for (i = 0; i < m; i = e) {
+        e = i + 1;
+        if (chains(b[i].r, tile_bytes))
+            while (e < m && follows(b[e - 1].r, b[e].r, 1)) ++e;
+        v[nv].pos1 = pos1[b[i].idx]; v[nv].idx = b[i].idx; v[nv].at = -1 - i; v[nv].k = e - i;
+        v[nv].kind = e - i > 1 ? XG_VIEW_SRC_STRIPED : XG_VIEW_SINGLE;
+        ++nv;
+    }
+    qsort(v, (size_t)nv, sizeof *v, cmp_view);
+    /* the views in order, a chain longer than kmax in consecutive views of kmax rows */
+    for (i = 0, e = 0; i < nv; ++i) {
+        const vent *from = v[i].at >= 0 ? a + v[i].at : b + (-1 - v[i].at);
+        int64_t kmax = 1, done, j;
+        if (v[i].k > 1) {
+            kmax = tile_bytes / from->r->len;
+            if (kmax > tile_pieces) kmax = tile_pieces;
+            if (kmax < 1) kmax = 1;
+        }
+        for (done = 0; done < v[i].k; done += kmax) {
+            const int64_t k = v[i].k - done < kmax ? v[i].k - done : kmax;
+            if (order)
+                for (j = 0; j < k; ++j) order[e + j] = from[done + j].idx;
+            e += k;
+            if (view_k) view_k[out] = (int32_t)k;
+            if (view_kind) view_kind[out] = k > 1 ? v[i].kind : XG_VIEW_SINGLE;
+            ++out;
+        }
+    }
+    free(a); free(b); free(pos1); free(v);
+    return out;
+}

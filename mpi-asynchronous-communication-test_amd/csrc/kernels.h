@@ -29,6 +29,8 @@
 //  copy_kernel_v      the same copy for strided runs: one workgroup per tile of one ROW (count blocks
 //                     of len bytes a step apart), every block derived by arithmetic -- no descriptor
 //                     per block; shares copy_kernel_x's scan and sweep (ext_tile_copy).
+//  copy_kernel_vv     the row copy with a tile dealt across the k rows of one striped VIEW, so that a
+//                     tile touches k x len contiguous bytes per block index on the striped side.
 //  step_engine_kernel a whole GPU-local run of small steps in one persistent
 //                     launch: bursts per step, grid barrier + wall-clock stamp between.
 //  solo_engine_kernel the same for small plans in ONE workgroup: workgroup barrier
@@ -1449,6 +1451,50 @@ __global__ __launch_bounds__(kThreads) void copy_kernel_v(const DVRow *__restric
                                         (int64_t)(t - tile0[lo]), (int)threadIdx.x);
     ext_tile_copy<NT>((uint64_t)(uintptr_t)r.src + (uint64_t)p.src_off, (uint64_t)(uintptr_t)r.dst + (uint64_t)p.dst_off,
                       (int)p.n);
+}
+
+// ---------------------------------------------------------------- view copy
+// copy_kernel_vv<NT>: copy_kernel_v with the tile dealt ACROSS the rows of a VIEW (xg_vrow_views: k
+// rows equal in len, count and steps whose offsets are len apart on one side -- a domain striped over
+// k ranks in runs of len bytes).  One workgroup per tile of one view:
+//   * workgroup base + blockIdx.x finds its view by the same uniform binary search over tile0
+//     (views + 1 entries, strictly increasing) and loads, uniformly, the view's 16-B record {row0, k,
+//     jb} and len, count and the steps of its first row -- every row of a view has the same;
+//   * lane q derives its (row i, block j) with xg_view_piece_at (xg_sched.h: the function the host
+//     tests walk): i = q % k, the fastest index, j = t * jb + q / k, the division by the uniform k in
+//     32 bits, everything else in 64.  The one table read per lane is the two pointers of device row
+//     row0 + i (the first 16 B of its record); there is still no descriptor per block.  A tile's
+//     pieces so ascend on the striped side: with stride == k * len the k * jb blocks of a tile are
+//     one interval there, whole lines where a tile of one row touches len bytes per stride;
+//   * the pieces are copied by ext_tile_copy, which every lane reaches, with its promises (above).
+// A view of one row is copy_kernel_v's deal exactly, long blocks (lane 0 alone, piece t) included.
+// tile_bytes: what the host dealt the tiles by.  base, start: as copy_kernel_v.
+template <bool NT = false>
+__global__ __launch_bounds__(kThreads) void copy_kernel_vv(const DVRow *__restrict__ rows,
+                                                           const DView *__restrict__ views,
+                                                           const int *__restrict__ tile0, int nviews, uint32_t base,
+                                                           int64_t tile_bytes, unsigned long long *start)
+{
+    if (start && blockIdx.x == 0 && threadIdx.x == 0) *start = (unsigned long long)wall_clock64();
+    const int t = (int)(base + blockIdx.x);
+    int lo = 0, hi = nviews - 1;                  // the last view with tile0 <= t
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (tile0[mid] <= t) lo = mid;
+        else hi = mid - 1;
+    }
+    const DView w = views[lo];
+    const DVRow *r0 = rows + w.row0;
+    const int64_t src_step = r0->src_step, dst_step = r0->dst_step;
+    const xg_view_at p = xg_view_piece_at(r0->len, r0->count, w.k, (int64_t)w.jb, tile_bytes, (int64_t)(t - tile0[lo]),
+                                          (int)threadIdx.x);
+    uint64_t s = 0, d = 0;
+    if (p.n) {                                    // p.row < k: a row of this view
+        const DVRow *r = r0 + p.row;
+        s = (uint64_t)(uintptr_t)r->src + (uint64_t)(p.block * src_step + p.off);
+        d = (uint64_t)(uintptr_t)r->dst + (uint64_t)(p.block * dst_step + p.off);
+    }
+    ext_tile_copy<NT>(s, d, (int)p.n);
 }
 
 }  // namespace xgk

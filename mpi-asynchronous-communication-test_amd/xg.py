@@ -307,7 +307,7 @@ def parse_tables(text):
     for line in text.splitlines():
         f = line.split()
         tag = f[0]
-        if tag in ("plan", "vec"):
+        if tag in ("plan", "vec", "views"):
             out[tag] = dict((f[i], val(f[i + 1])) for i in range(1, len(f), 2))
         elif tag == "step":
             names = ("stage", "local", "pack", "post", "calls", "bytes", "l")
@@ -411,6 +411,84 @@ class VecTables:
     def records(self):
         """the dump by record tag, as parse_tables gives a plan's: "vec" a dict, "row" lists of
         [(buf, off) src, (buf, off) dst, src_step, dst_step, len, count], "tile0" / "cut" / "dbytes" ints"""
+        return parse_tables(self.dump())
+
+
+class ViewTables:
+    """The tables xg_vecplace_load_views builds from a GPU's row list, built with no GPU
+    (xg_view_tables_build, csrc/host/vec_tables.cc): the rows in view order, a record per view, tile0
+    over the views, the dispatch cuts.  Arguments and XGError as VecTables."""
+    _lib = None
+
+    @classmethod
+    def lib(cls):
+        if cls._lib is None:
+            h = host()
+            T, i64 = C.c_void_p, C.c_int64
+            h.xg_view_tables_build.argtypes = [C.POINTER(VRow), i64, C.POINTER(C.c_uint64), C.POINTER(i64), i64, C.c_int,
+                                               i64, C.POINTER(T)]
+            h.xg_view_tables_free.restype = None
+            h.xg_view_tables_free.argtypes = [T]
+            for fn in ("rows", "views", "multi", "tiles", "bytes"):
+                getattr(h, "xg_view_tables_" + fn).restype = i64
+                getattr(h, "xg_view_tables_" + fn).argtypes = [T]
+            h.xg_view_tables_dispatches.argtypes = [T]
+            for fn in ("cut", "dispatch_bytes"):
+                getattr(h, "xg_view_tables_" + fn).restype = i64
+                getattr(h, "xg_view_tables_" + fn).argtypes = [T, C.c_int]
+            h.xg_view_tables_order.restype = i64
+            h.xg_view_tables_order.argtypes = [T, i64]
+            h.xg_view_tables_dump.restype = i64
+            h.xg_view_tables_dump.argtypes = [T, C.c_char_p, i64]
+            cls._lib = h
+        return cls._lib
+
+    def __init__(self, rows, nbytes, base=None, tile_bytes=32768, tile_pieces=256, launch_max=512 << 20):
+        h = self.lib()
+        arr, n = _vrow_array(rows)
+        self.base = list(base) if base is not None else [(b + 1) << 40 for b in range(NBUF)]
+        self.nbytes = list(nbytes) + [0] * (NBUF - len(nbytes))
+        self.h = C.c_void_p()
+        rc = h.xg_view_tables_build(arr, n, (C.c_uint64 * NBUF)(*self.base), (C.c_int64 * NBUF)(*self.nbytes), tile_bytes,
+                                    tile_pieces, launch_max, C.byref(self.h))
+        if rc:
+            raise XGError("xg_view_tables_build: %d" % rc)
+
+    def close(self):
+        if self.h:
+            self.lib().xg_view_tables_free(self.h)
+            self.h = C.c_void_p()
+
+    __del__ = close
+
+    rows = property(lambda self: self.lib().xg_view_tables_rows(self.h))
+    views = property(lambda self: self.lib().xg_view_tables_views(self.h), doc="all views")
+    multi = property(lambda self: self.lib().xg_view_tables_multi(self.h), doc="the views of more than one row")
+    tiles = property(lambda self: self.lib().xg_view_tables_tiles(self.h))
+    dispatches = property(lambda self: self.lib().xg_view_tables_dispatches(self.h))
+    bytes = property(lambda self: self.lib().xg_view_tables_bytes(self.h))
+
+    def cuts(self):
+        """the dispatches' tile boundaries: dispatches + 1 entries from 0 to tiles"""
+        return [self.lib().xg_view_tables_cut(self.h, k) for k in range(self.dispatches + 1)]
+
+    def dispatch_bytes(self):
+        return [self.lib().xg_view_tables_dispatch_bytes(self.h, k) for k in range(self.dispatches)]
+
+    def order(self):
+        """the list index of every device row"""
+        return [self.lib().xg_view_tables_order(self.h, i) for i in range(self.rows)]
+
+    def dump(self):
+        h = self.lib()
+        n = h.xg_view_tables_dump(self.h, None, 0)
+        buf = C.create_string_buffer(n + 1)
+        h.xg_view_tables_dump(self.h, buf, n + 1)
+        return buf.value.decode()
+
+    def records(self):
+        """the dump by record tag: "views" a dict, "row" as VecTables', "order" ints, "view" lists of
+        [row0, k, jb, kind], "tile0" / "cut" / "dbytes" ints"""
         return parse_tables(self.dump())
 
 
@@ -548,6 +626,13 @@ def host():
         h.xg_vec_piece.argtypes = [C.POINTER(VRow), C.c_int64, C.c_int, C.c_int64, C.c_int] + [C.POINTER(C.c_int64)] * 3
         h.xg_vec_rows_tiles.argtypes = [C.POINTER(VRow), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int32)]
         h.xg_vec_rows_tiles.restype = C.c_int64
+        h.xg_vrow_views.argtypes = [C.POINTER(VRow), C.c_int64, C.c_int64, C.c_int, C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        h.xg_vrow_views.restype = C.c_int64
+        h.xg_view_tiles.argtypes = [C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int]
+        h.xg_view_tiles.restype = C.c_int64
+        h.xg_view_piece.argtypes = [C.POINTER(VRow), C.c_int, C.c_int64, C.c_int, C.c_int64, C.c_int, C.POINTER(C.c_int)] + \
+            [C.POINTER(C.c_int64)] * 3
         h.xg_fill_runs.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(SegRun)]
         h.xg_verify_slots.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(Slot)]
         h.xg_deliveries.argtypes = [C.c_void_p, C.c_int, C.POINTER(Delivery)]
@@ -873,6 +958,41 @@ def vec_rows_tiles(rows, tile_bytes=32768, tile_pieces=256):
     if host().xg_vec_rows_tiles(arr, n, tile_bytes, tile_pieces, t0) < 0:
         return None
     return list(t0)
+
+
+VIEW_SINGLE, VIEW_DST_STRIPED, VIEW_SRC_STRIPED = 0, 1, 2      # XG_VIEW_*
+
+
+def vrow_views(rows, tile_bytes=32768, tile_pieces=256):
+    """xg_vrow_views: the rows of a list grouped into views -> [(kind, [list indices of the view's
+    rows, ascending on the striped side])], in view order"""
+    arr, n = _vrow_array(rows)
+    order, k, kind = (C.c_int64 * max(1, n))(), (C.c_int32 * max(1, n))(), (C.c_int32 * max(1, n))()
+    nv = host().xg_vrow_views(arr, n, tile_bytes, tile_pieces, order, k, kind)
+    if nv < 0:
+        raise XGError("xg_vrow_views: bad arguments or out of host memory")
+    out, at = [], 0
+    for v in range(nv):
+        out.append((kind[v], list(order[at:at + k[v]])))
+        at += k[v]
+    assert at == n
+    return out
+
+
+def view_tiles(length, count, k, tile_bytes=32768, tile_pieces=256):
+    """xg_view_tiles: the tiles (one workgroup each) of a view of k rows"""
+    return host().xg_view_tiles(length, count, k, tile_bytes, tile_pieces)
+
+
+def view_piece(rows, t, q, tile_bytes=32768, tile_pieces=256):
+    """xg_view_piece: (row, src_off, dst_off, n) of lane q of tile t of the view made of `rows` (in
+    view order, or a VRow array made once for many calls; n = 0: the lane is idle); None when the rows
+    are no view, t is no tile of it or q no lane"""
+    arr, k = (rows, len(rows)) if isinstance(rows, C.Array) else _vrow_array(rows)
+    row, out = C.c_int(), [C.c_int64() for _ in range(3)]
+    if host().xg_view_piece(arr, k, tile_bytes, tile_pieces, t, q, C.byref(row), *[C.byref(x) for x in out]) != 0:
+        return None
+    return (row.value,) + tuple(x.value for x in out)
 
 
 def method_label(method):
@@ -1257,6 +1377,11 @@ def device():
         d.xg_vecplace_tiles.restype = i64
         d.xg_vecplace_tiles.argtypes = [vp]
         d.xg_vecplace_dispatches.argtypes = [vp]
+        d.xg_vecplace_load_views.argtypes = [vp, vp, C.POINTER(VRow), i64, C.POINTER(vp)]
+        d.xg_vecplace_views.restype = i64
+        d.xg_vecplace_views.argtypes = [vp]
+        d.xg_exchange_wv_views.restype = i64
+        d.xg_exchange_wv_views.argtypes = []
         d.xg_plan_displs.argtypes = [vp, C.POINTER(i64), ip]
         d.xg_ktime_begin.argtypes = [vp, ip, ip]
         d.xg_ktime_end.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(ip), C.POINTER(i64)]
@@ -1666,13 +1791,20 @@ def vec_tiles():
     return device().xg_exchange_wv_tiles()
 
 
+def exchange_wv_views():
+    """xg_exchange_wv_views: the views of more than one row of this process's last exchange_wv
+    placement (0 unless XG_VEC_VIEWS=1 loaded it by views)"""
+    return device().xg_exchange_wv_views()
+
+
 class VecPlace:
     """One GPU's strided placement on its own: rows (VRow records or tuples; Schedule.vec_rows gives
-    a vec list's) loaded as one copy_kernel_v launch (xg_vecplace_load) over regions of region_bytes
+    a vec list's) loaded as one copy_kernel_v launch (xg_vecplace_load) or, with views=True, as one
+    copy_kernel_vv launch over the list's views (xg_vecplace_load_views), over regions of region_bytes
     whose SEND / RECV are the caller's (addresses as int) or allocated here.  XGError for rows the
     host builder refuses: nothing has run then."""
 
-    def __init__(self, ctx, rows, region_bytes, send=None, recv=None, vec_index=None):
+    def __init__(self, ctx, rows, region_bytes, send=None, recv=None, vec_index=None, views=False):
         d = device()
         self.ctx = ctx
         self.rows = [r if isinstance(r, VRow) else VRow(*[int(x) for x in r]) for r in rows]
@@ -1682,11 +1814,12 @@ class VecPlace:
         self._r = self.regions._r
         self._v = C.c_void_p()
         arr, n = _vrow_array(self.rows)
-        rc = d.xg_vecplace_load(ctx.handle, self._r, arr, n, C.byref(self._v))
+        load = d.xg_vecplace_load_views if views else d.xg_vecplace_load
+        rc = load(ctx.handle, self._r, arr, n, C.byref(self._v))
         if rc:
             self.regions.close()
             self.regions = None
-            raise XGError("xg_vecplace_load failed with code %d (see stderr)" % rc)
+            raise XGError("xg_vecplace_load%s failed with code %d (see stderr)" % ("_views" if views else "", rc))
 
     def run(self):
         """one timed run -> the launch's device seconds"""
@@ -1701,6 +1834,11 @@ class VecPlace:
     @property
     def dispatches(self):
         return _dev.xg_vecplace_dispatches(self._v)
+
+    @property
+    def views(self):
+        """the views of more than one row (0 unless loaded with views=True)"""
+        return _dev.xg_vecplace_views(self._v)
 
     def close(self):
         if getattr(self, "_v", None):
